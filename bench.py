@@ -3,10 +3,15 @@
 One step = one NeRF training iteration on a synthetic Lego-like batch (BASELINE config 2:
 8192 rays/batch per GPU, Hash grid L=16 F=2 T=2^19, rgb 64x2): AABB -> ray march -> grid encode
 -> MFMA field head -> composite -> loss -> composite bw -> field bw -> grid bw -> [all-reduce] ->
-Adam.  The timed steps replay the step as three HIP graphs (mfnerf.engine.TrainStep.capture);
-a preceding eager pass gives the per-kernel breakdown (eager_stage_ms).  The occupancy-grid
-refresh (every 16 steps in the reference) is excluded from the timed step as SURVEY.md 8d
-prescribes and reported separately (density_update_ms, value_with_occupancy_refresh).
+Adam.  The timed steps replay the step as HIP graphs (mfnerf.engine.TrainStep.capture).  The
+occupancy-grid refresh (every 16 steps in the reference) is excluded from the timed step as
+SURVEY.md 8d prescribes.
+
+A plain run does what the headline figure needs and no more: set-up, warm-up, the K timed steps,
+the outputs (--dump-outputs DIR: what the last timed step computed, as DIR/<name>.npy) and one JSON
+line.  --full adds everything else the line can hold: the per-kernel breakdown of an eager pass
+(eager_stage_ms), the occupancy refresh's cost (density_update_ms, value_with_occupancy_refresh),
+the grid_bw roofline (event-timed scatter launches inside the timed steps) and the CPU baselines.
 
 python bench.py [--gpus N --steps K --warmup W]; N>1 runs one rank per GPU (rank-distinct rays,
 reduce-scatter of the flat fp32 gradient + sharded Adam + fp16 all-gather per step over RCCL):
@@ -69,10 +74,16 @@ def parse(argv=None):
     ap.add_argument("--preset", choices=sorted(PRESETS), default="lego")
     ap.add_argument("--n-rays", type=int, default=None, help="override the preset's rays per GPU")
     ap.add_argument("--log2-T", type=int, default=None, help="override the preset's log2 table size")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the eager per-stage breakdown, "
+                         "the occupancy refresh, the grid_bw roofline and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (the batch it drew, the "
+                         "rendered rays, the loss, the updated parameters) as DIR/<name>.npy")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: seconds per CPU baseline sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--roofline-every", type=int, default=25,
-                    help="time grid_bw with events on every k-th timed step (those steps replay the scatter "
+                    help="--full: time grid_bw with events on every k-th timed step (those steps replay the scatter "
                          "as its own graph, ~45 us more per such step than the one-graph step (r4h: 0.5645 "
                          "ms/step at k = 8 vs 0.5588 at k = 1000); the others replay the whole step as one "
                          "graph); 25: 8 timed launches in the default 200 steps")
@@ -254,6 +265,43 @@ def cpu_baseline(n_rays, log2_T, seconds, grid="Hash", n_tables=1, width=64, lr=
                       f" fp32 torch-CPU field + C oracle march/compositing ({el:.1f} s)"}
 
 
+DUMP_TABLE_VALUES = 1 << 23  # --dump-outputs: at most this many table values (32 MB of fp32)
+
+
+def write_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy, fp32 (fp64 kept)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float64 if a.dtype == np.float64 else np.float32))
+
+
+def step_outputs(step, params):
+    """What the step that ran last left for its caller (host-synchronising): the batch it drew, the
+    rendered rays, the loss and the updated fp32 parameters `params` -- of the hash table, when it
+    holds more than DUMP_TABLE_VALUES values, a fixed seeded sample of that many (sorted indices, a
+    function of the table size alone)."""
+    import numpy as np
+    torch.cuda.synchronize()
+    parts = step.state.parts
+    out = {
+        "batch": step.last_batch.buf,  # (3, N, 3): rays_o, rays_d, target rgb
+        "rgb": torch.cat([t.rgb for t in parts]),
+        "opacity": torch.cat([t.opacity for t in parts]),
+        "depth": torch.cat([t.depth for t in parts]),
+        "samples_per_ray": torch.cat([t.total for t in parts]).double(),
+        "loss": step.loss_sum.double().reshape(1),
+        "params_mlp": params[:step.off_table],
+    }
+    table = params[step.off_table:step.n_params]
+    if table.numel() > DUMP_TABLE_VALUES:
+        idx = np.sort(np.random.default_rng(0).integers(0, table.numel(), DUMP_TABLE_VALUES))
+        table = table[torch.from_numpy(idx).to(table.device)]
+    out["params_table"] = table
+    return out
+
+
 def line_base(args, pre, world, elapsed, mean_samples, dp_on=False):
     """The driver-contract fields of the JSON line (value = rays of ALL ranks / slowest rank's time)."""
     rays_total = args.n_rays * args.steps * world
@@ -316,10 +364,68 @@ def stub_main(args, world, rank, out_fd):
     if rank == 0:
         out = line_base(args, pre, world, max(elapsed, 1e-9), 0.0, dp_on=world > 1)
         out["data"] = "stub (launcher test: no GPU step ran)"
+        if args.dump_outputs:
+            write_outputs(args.dump_outputs, {"x": x})
         with os.fdopen(out_fd, "w") as f:
             f.write(json.dumps(out) + "\n")
     if world > 1:
         dist.destroy_process_group()
+
+
+def full_fields(args, pre, world, step, elapsed, mean_samples, use_graph, every, gb_ev, eager_ev, eager_stage_ms,
+                density_ms):
+    """--full: the line's fields beyond the headline figure (rank 0): the grid_bw roofline from the
+    event-timed scatter launches of the timed steps, the eager pass's per-stage times, the occupancy
+    refresh and the CPU baselines (which run here, after the timed region)."""
+    rays_total = args.n_rays * args.steps * world
+    if use_graph and every:
+        # the parts' grid_bw scatters run back to back (part q+1's chain overlaps part q's): time
+        # from the first one's start to the last one's end
+        sampled = gb_ev[::every]
+        grid_bw_ms = sum(max(a.elapsed_time(b) for b in ends) for a, ends in sampled) / len(sampled)
+    elif use_graph:
+        grid_bw_ms = None  # --roofline-every 0: no scatter launch was timed
+    else:
+        grid_bw_ms = stage_times(eager_ev, args.steps)["grid_bw"]
+    roofline = None
+    if grid_bw_ms:
+        # roofline: grid_bw (the dominant kernel), timed by events around it inside the timed region
+        dom = "grid_bw"
+        # the newest committed PMC summary of this preset's workload
+        traffic, atomic_req, traffic_src = pmc_traffic(GRID_BW_KERNEL, args.preset, args.log2_T, args.n_rays)
+        dom_bytes = BYTES_PER_SAMPLE[dom] * mean_samples
+        achieved = dom_bytes / (grid_bw_ms * 1e-3) / 1e9
+        # the bound the scatter actually meets: memory-side atomic requests per second
+        atomic = None
+        if atomic_req:
+            rate = atomic_req / (grid_bw_ms * 1e-3) / 1e9
+            atomic = {"requests_per_launch": round(atomic_req),
+                      "requests_per_sample": round(atomic_req / mean_samples, 2),
+                      "achieved": round(rate, 2), "peak": ATOMIC_REQ_PEAK_G, "unit": "G requests/s",
+                      "frac": round(rate / ATOMIC_REQ_PEAK_G, 4)}
+        roofline = {"bound": "hbm", "kernel": dom + " (" + "+".join(GRID_BW_KERNEL) + ")",
+                    "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+                    "traffic_source": traffic_src,
+                    "timed_launches": len(range(0, args.steps, every)) if use_graph else args.steps,
+                    "bytes_per_launch": round(dom_bytes), "bytes_per_sample": BYTES_PER_SAMPLE[dom],
+                    "samples_per_launch": round(mean_samples), "atomic": atomic}
+    cpu = None
+    if not args.no_cpu_baseline and world == 1:
+        # SURVEY.md 8(d): the host path on the bench's own batch (8192 rays x ~60 samples, fw+bw+Adam)
+        # and on config 1's 256-ray batch, each a bounded sample of the CPUs given to the run
+        hp = (pre["grid"], pre["N_tables"], pre["rgb_width"], pre["lr"])
+        cpu = cpu_baseline(args.n_rays, args.log2_T, args.cpu_seconds, *hp, min_timed=1)
+        cpu["other_batches"] = [cpu_baseline(256, args.log2_T, args.cpu_seconds / 2, *hp)]
+    return {
+        "roofline": roofline,
+        "grid_bw_ms": round(grid_bw_ms, 4) if grid_bw_ms else None,
+        "eager_stage_ms": {k: round(v, 4) for k, v in eager_stage_ms.items()},
+        "density_update_ms": round(density_ms, 3),
+        # the reference refreshes occupancy every 16 steps (train.py:62,165): rate with it amortised
+        "value_with_occupancy_refresh": round(rays_total / (elapsed + args.steps / 16 * density_ms * 1e-3), 1),
+        "cpu_baseline": cpu,
+    }
 
 
 def main(argv=None):
@@ -382,36 +488,42 @@ def main(argv=None):
 
     for i in range(args.warmup):
         run_step(step, batches[i % len(batches)], world, allreduce=dp_on)
-    # occupancy refresh cost (amortised every 16 steps in the reference), measured separately
-    step.update_density_grid(warmup=False)  # first call allocates the refresh scratch
-    torch.cuda.synchronize()
-    td = time.time()
-    for _ in range(10):
-        step.update_density_grid(warmup=False)
-    torch.cuda.synchronize()
-    density_ms = (time.time() - td) / 10 * 1e3
-    step.set_occupancy(synthetic.ball_density_grid())  # keep the calibrated workload for the timed steps
+    density_ms = None
+    if args.full:
+        # occupancy refresh cost (amortised every 16 steps in the reference), measured separately
+        step.update_density_grid(warmup=False)  # first call allocates the refresh scratch
+        torch.cuda.synchronize()
+        td = time.time()
+        for _ in range(10):
+            step.update_density_grid(warmup=False)
+        torch.cuda.synchronize()
+        density_ms = (time.time() - td) / 10 * 1e3
+        step.set_occupancy(synthetic.ball_density_grid())  # keep the calibrated workload for the timed steps
 
-    # per-stage breakdown from an eager pass (an event after every kernel stage)
+    # an eager pass of min(K, 50) steps; --full: an event after every kernel stage of it, the
+    # per-stage breakdown.  A plain run takes the same steps unobserved: the model trains during
+    # the bench and the step gets cheaper as it does (below), so the timed steps of a plain and a
+    # --full run start from the same point of training and their lines are comparable
     n_eager = min(args.steps, 50)
     pass_ev = []
     for i in range(n_eager):
-        ev = []
+        ev = [] if args.full else None
         run_step(step, batches[i % len(batches)], world, ev, allreduce=dp_on)
         pass_ev.append(ev)
     torch.cuda.synchronize()
-    eager_stage_ms = stage_times(pass_ev, n_eager)
+    eager_stage_ms = stage_times(pass_ev, n_eager) if args.full else None
 
     # the timed region: the step replayed from HIP graphs (launch overhead off the host); the only
-    # per-step host work is the batch copy, three graph launches and two pre-created timing events
-    # around the grid_bw graph (the roofline kernel)
+    # per-step host work is the graph launches and, --full, on every --roofline-every-th step two
+    # pre-created timing events around the grid_bw graph (the roofline kernel)
     from mfnerf import dp as _dp
     ex = _dp.allreduce_mean_ if dp_on else None
     use_graph = not args.eager
+    every = args.roofline_every if args.full else 0  # 0: no step's scatter is event-timed
     if use_graph:
         step.capture()
-        # the first replays of fresh graphs run slow: settle before timing -- both forms the timed
-        # steps replay, the one-graph step and the split step whose scatter the events time.
+        # the first replays of fresh graphs run slow: settle before timing -- every form the timed
+        # steps replay: the one-graph step and, --full, the split step whose scatter the events time.
         # (A 20-step line runs ~5 % slower per step than a 200-step one, and that is the workload, not
         # a start-up cost: the model trains during the bench, and once densities are learned rays
         # terminate earlier in compositing, so fewer samples carry a table gradient -- per-step time
@@ -419,9 +531,9 @@ def main(argv=None):
         warm_ev = (torch.cuda.Event(enable_timing=True), [torch.cuda.Event(enable_timing=True)
                                                           for _ in range(step.n_parts)])
         for i in range(24):
-            step.replay(exchange=ex, grid_bw_events=warm_ev if i % 4 == 1 else None)
+            step.replay(exchange=ex, grid_bw_events=warm_ev if every and i % 4 == 1 else None)
     mk = lambda: torch.cuda.Event(enable_timing=True)  # noqa: E731
-    gb_ev = [(mk(), [mk() for _ in range(step.n_parts)]) for _ in range(args.steps)]
+    gb_ev = [(mk(), [mk() for _ in range(step.n_parts)]) for _ in range(args.steps if every else 0)]
     eager_ev = []
     if world > 1:
         torch.distributed.barrier()
@@ -432,10 +544,10 @@ def main(argv=None):
         if use_graph:
             # the next step's batch draw + march overlap this step's grid_bw (the last one draws
             # and marches the batch after the timed steps: extra work inside the timed region)
-            timed = i % args.roofline_every == 0
+            timed = every and i % every == 0
             step.replay(exchange=ex, grid_bw_events=gb_ev[i] if timed else None)
         else:
-            ev = []
+            ev = [] if args.full else None
             run_step(step, batches[i % len(batches)], world, ev, allreduce=dp_on)
             eager_ev.append(ev)
     host_s = time.time() - t0  # the host's issue time for the K steps (GPU-bound when well below elapsed)
@@ -444,60 +556,24 @@ def main(argv=None):
         torch.distributed.barrier()
     elapsed = time.time() - t0
     elapsed = dp.max_over_ranks(elapsed, dev)  # the slowest rank's clock
-    if use_graph:
-        # the parts' grid_bw scatters run back to back (part q+1's chain overlaps part q's): time
-        # from the first one's start to the last one's end
-        sampled = gb_ev[::args.roofline_every]
-        grid_bw_ms = sum(max(a.elapsed_time(b) for b in ends) for a, ends in sampled) / len(sampled)
-    else:
-        grid_bw_ms = stage_times(eager_ev, args.steps)["grid_bw"]
     # one batch is marched per timed step (the graphs march the next step's batch)
     mean_samples = (int(step.samples_marched) - marched0) / args.steps
-    rays_total = args.n_rays * args.steps * world
-
-    # roofline: grid_bw (the dominant kernel), timed by events around it inside the timed region
-    dom = "grid_bw"
-    # the newest committed PMC summary of this preset's workload
-    traffic, atomic_req, traffic_src = pmc_traffic(GRID_BW_KERNEL, args.preset, args.log2_T, args.n_rays)
-    dom_bytes = BYTES_PER_SAMPLE[dom] * mean_samples
-    achieved = dom_bytes / (grid_bw_ms * 1e-3) / 1e9
-    # the bound the scatter actually meets: memory-side atomic requests per second
-    atomic = None
-    if atomic_req:
-        rate = atomic_req / (grid_bw_ms * 1e-3) / 1e9
-        atomic = {"requests_per_launch": round(atomic_req), "requests_per_sample": round(atomic_req / mean_samples, 2),
-                  "achieved": round(rate, 2), "peak": ATOMIC_REQ_PEAK_G, "unit": "G requests/s",
-                  "frac": round(rate / ATOMIC_REQ_PEAK_G, 4)}
+    if args.dump_outputs:
+        params = step.full_params()  # (sharded: a collective, so on every rank)
+        if rank == 0:
+            write_outputs(args.dump_outputs, step_outputs(step, params))
     if rank == 0:
-        cpu = None
-        if not args.no_cpu_baseline and world == 1:
-            # the host path on the bench's own batch (8192 rays x ~60 samples, fw+bw+Adam)
-            # and on config 1's 256-ray batch, each a bounded sample on the box's CPU share
-            hp = (pre["grid"], pre["N_tables"], pre["rgb_width"], pre["lr"])
-            cpu = cpu_baseline(args.n_rays, args.log2_T, args.cpu_seconds, *hp, min_timed=1)
-            cpu["other_batches"] = [cpu_baseline(256, args.log2_T, args.cpu_seconds / 2, *hp)]
         out = line_base(args, pre, world, elapsed, mean_samples, dp_on)
         out["config"]["exchange"] = (None if not dp_on else "rccl-direct, one graph per step" if direct
                                      else "torch.distributed between graphs")
         out.update({
-            "roofline": {"bound": "hbm", "kernel": dom + " (" + "+".join(GRID_BW_KERNEL) + ")",
-                         "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-                         "traffic_source": traffic_src,
-                         "timed_launches": (len(range(0, args.steps, args.roofline_every)) if use_graph
-                                            else args.steps),
-                         "bytes_per_launch": round(dom_bytes), "bytes_per_sample": BYTES_PER_SAMPLE[dom],
-                         "samples_per_launch": round(mean_samples), "atomic": atomic},
-            "graph": use_graph, "host_issue_ms_per_step": round(host_s / args.steps * 1e3, 4),
-            "grid_bw_ms": round(grid_bw_ms, 4),
+            "full": args.full, "graph": use_graph, "host_issue_ms_per_step": round(host_s / args.steps * 1e3, 4),
             # gated marches that gave up waiting (gate.hip): 0 unless a step stalled GATE_TIMEOUT_US
             "gate_timeouts": step.gate_timeouts() if use_graph else None,
-            "eager_stage_ms": {k: round(v, 4) for k, v in eager_stage_ms.items()},
-            "density_update_ms": round(density_ms, 3),
-            # the reference refreshes occupancy every 16 steps (train.py:62,165): rate with it amortised
-            "value_with_occupancy_refresh": round(rays_total / (elapsed + args.steps / 16 * density_ms * 1e-3), 1),
-            "cpu_baseline": cpu,
         })
+        if args.full:
+            out.update(full_fields(args, pre, world, step, elapsed, mean_samples, use_graph, every, gb_ev, eager_ev,
+                                   eager_stage_ms, density_ms))
         with os.fdopen(out_fd, "w") as f:
             f.write(json.dumps(out) + "\n")
     if dp_on:

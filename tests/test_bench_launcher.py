@@ -41,6 +41,17 @@ def test_gpus_1_runs_in_process():
     assert d["n_gpus"] == 1 and d["config"]["global_batch"] == 8192
 
 
+def test_full_and_dump_outputs_are_options(tmp_path):
+    import numpy as np
+    out = tmp_path / "outputs"  # created by the run
+    r = _run(["--gpus", "1", "--stub-step", "--steps", "2", "--warmup", "0", "--full", "--dump-outputs", str(out)])
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = json.loads(r.stdout)
+    assert d["steps"] == 2 and d["ms_per_step"] > 0
+    assert [f.name for f in out.iterdir()] == ["x.npy"]
+    assert np.load(out / "x.npy").dtype == np.float32
+
+
 def test_world_size_must_match_gpus():
     r = _run(["--gpus", "4", "--stub-step", "--steps", "1", "--warmup", "0"], WORLD_SIZE="2", RANK="0",
              LOCAL_RANK="0")

@@ -20,16 +20,16 @@ for s in $STEPS; do
       timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > $D/smoke.log 2>&1 || { tail -20 $D/smoke.log; exit 1; }
       tail -1 $D/smoke.log ;;
     bench)
-      timeout -k 10 400 python bench.py > $D/bench.json 2> $D/bench.err || { tail -20 $D/bench.err; exit 1; }
+      timeout -k 10 400 python bench.py --full > $D/bench.json 2> $D/bench.err || { tail -20 $D/bench.err; exit 1; }
       line $D/bench.json ;;
     mf128)
-      timeout -k 10 200 python bench.py --no-cpu-baseline --preset mf128 > $D/bench_mf128.json 2> $D/bench_mf128.err || { tail -20 $D/bench_mf128.err; exit 1; }
+      timeout -k 10 200 python bench.py --full --no-cpu-baseline --preset mf128 > $D/bench_mf128.json 2> $D/bench_mf128.err || { tail -20 $D/bench_mf128.err; exit 1; }
       line $D/bench_mf128.json ;;
     T20)
-      timeout -k 10 200 python bench.py --no-cpu-baseline --log2-T 20 > $D/bench_T20.json 2> $D/bench_T20.err || { tail -20 $D/bench_T20.err; exit 1; }
+      timeout -k 10 200 python bench.py --full --no-cpu-baseline --log2-T 20 > $D/bench_T20.json 2> $D/bench_T20.err || { tail -20 $D/bench_T20.err; exit 1; }
       line $D/bench_T20.json ;;
     dp)
-      timeout -k 10 200 python bench.py --no-cpu-baseline --dp-rehearse > $D/bench_dp_rehearse.json 2> $D/bench_dp_rehearse.err || { tail -20 $D/bench_dp_rehearse.err; exit 1; }
+      timeout -k 10 200 python bench.py --full --no-cpu-baseline --dp-rehearse > $D/bench_dp_rehearse.json 2> $D/bench_dp_rehearse.err || { tail -20 $D/bench_dp_rehearse.err; exit 1; }
       line $D/bench_dp_rehearse.json ;;
     train30k)
       timeout -k 10 400 python tools/train_30k.py > $D/train30k.json 2> $D/train30k.err || { tail -20 $D/train30k.err; exit 1; }

@@ -8,7 +8,7 @@ mkdir -p gpurun_out
 export TMPDIR=/tmp
 P=${PRESET:-lego}
 X=$(python3 -c "import bench; print(bench.pmc_suffix('$P', ${LOG2T:-None}, None))")
-B="python3 bench.py --preset $P ${LOG2T:+--log2-T $LOG2T} --steps 20 --warmup 5 --no-cpu-baseline --roofline-every 1"  # every scatter launch unfused, as the timed ones
+B="python3 bench.py --preset $P ${LOG2T:+--log2-T $LOG2T} --steps 20 --warmup 5 --full --no-cpu-baseline --roofline-every 1"  # every scatter launch unfused, as the timed ones
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d gpurun_out/prof$X -o run --output-format csv -- $B > gpurun_out/prof$X.log 2>&1 && \
 timeout -s KILL 200 rocprofv3 --pmc FETCH_SIZE -d gpurun_out/pmc_fetch$X -o run --output-format csv -- $B > gpurun_out/pmc_fetch$X.log 2>&1 && \
 timeout -s KILL 200 rocprofv3 --pmc WRITE_SIZE -d gpurun_out/pmc_write$X -o run --output-format csv -- $B > gpurun_out/pmc_write$X.log 2>&1 && \
