@@ -332,6 +332,28 @@ int mfnerf_field_fw_density_scatter(const void* feat_f16, int64_t feat_plane_str
                                     const void* packed, int rgb_width, float* sigma, const int32_t* cell_idx,
                                     float* tmp, mfnerf_stream_t stream);
 
+/* The whole test-time renderer in one persistent launch: rendering.py:46-118 (the progressive loop
+ * over raymarching_test / the field / composite_test_fw) with its prologue, rendering.py:27-29 (the
+ * ray/box test for ONE box, center and half_size (3) f32 on the device, and the near clamp).  Each
+ * ray is marched (raymarching.cu:335-404, including the calc_dt(..., cascades) quirk; max_samples_dt
+ * is calc_dt's 1024), encoded (mfnerf_grid_encode_fw's arithmetic on x' = (x - x_min) / x_range),
+ * evaluated (mfnerf_field_fw, packed_weights from mfnerf_field_pack_weights, rgb_width 64 or 128)
+ * and composited (volumerendering.cu:205-285, T a running product from 1) sample by sample until
+ * T <= T_threshold, it leaves the box or ray_budget samples were evaluated.  No intermediate is
+ * written to memory.  The grid must have n_levels * n_features == 32.
+ * out: opacity, depth (n_rays), rgb (n_rays,3) f32 -- the un-blended sums (zeros for a ray that
+ *      misses the box); samples (n_rays) i32, optional, the evaluated samples of each ray;
+ *      total_samples (1) i64 = their sum.  queue (1) i32 is the launch's ray counter: it and
+ *      total_samples are zeroed by the launch itself (a kernel), so a replayed graph needs no reset.
+ * A ray's outputs do not depend on the rest of the batch.  n_rays == 0: nothing is launched. */
+int mfnerf_render_test_fused(const float* rays_o, const float* rays_d, int64_t n_rays, const float* center,
+                             const float* half_size, const uint8_t* bitfield, int cascades, float scale,
+                             float exp_step_factor, int grid_size, int max_samples_dt, int ray_budget,
+                             float T_threshold, float x_min, float x_range, const mfnerf_grid_desc* grid_desc,
+                             const void* table_f16, const void* packed_weights, int rgb_width, int32_t* queue,
+                             float* opacity, float* depth, float* rgb, int32_t* samples, int64_t* total_samples,
+                             mfnerf_stream_t stream);
+
 /* Backward of mfnerf_field_fw (recomputes the forward; same feat layouts).  dL_dsigma (n), dL_drgb (n,3) f32 ->
  * dL_dfeat (n,32) f32, and ADDS the weight grads into grad_xyz / grad_rgb (tcnn layout f32).
  * grad_scale: the loss scale -- factor applied to the incoming grads before the fp16 MFMA products

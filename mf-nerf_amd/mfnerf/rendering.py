@@ -95,6 +95,55 @@ def _render_rays_test(model, rays_o, rays_d, hits_t, **kwargs):
     return results
 
 
+@torch.no_grad()
+def render_fused(model, rays_o, rays_d, **kwargs):
+    """The test-time render (render(test_time=True): rendering.py:27-29 + :46-118) in one persistent
+    kernel launch, mfnerf_render_test_fused: ray/box test, march, grid encode, field head and
+    compositing per ray, no intermediate in memory, no host sync -- legal inside a captured graph
+    (every output is allocated here, before the launch).
+
+    Same kwargs as the test path (exp_step_factor, T_threshold, max_samples, to_cpu, to_numpy) and
+    the same result keys, plus `samples` (int32 per ray).  Two differences from the loop:
+    max_samples is a PER-RAY budget of evaluated samples (the loop caps the sum of its rounds' chunk
+    sizes), and total_samples (a 0-d device tensor) counts the samples the field evaluated, i.e.
+    samples.sum() (the loop also counts those marched past a ray's termination inside a chunk)."""
+    from . import field
+    from ._lib import call, check_input, ptr, stream
+    rays_o = rays_o.contiguous()
+    rays_d = rays_d.contiguous()
+    check_input("rays_o", rays_o, torch.float32)
+    check_input("rays_d", rays_d, torch.float32)
+    if rays_o.dim() != 2 or rays_o.shape[1] != 3 or rays_d.shape != rays_o.shape:
+        raise RuntimeError("rays_o and rays_d must both be (N, 3)")
+    exp_step_factor = kwargs.get("exp_step_factor", 0.0)
+    N_rays = rays_o.shape[0]
+    device = rays_o.device
+    opacity = torch.empty(N_rays, device=device)
+    depth = torch.empty(N_rays, device=device)
+    rgb = torch.empty(N_rays, 3, device=device)
+    samples = torch.empty(N_rays, dtype=torch.int32, device=device)
+    total_samples = torch.zeros((), dtype=torch.int64, device=device)
+    queue = torch.empty(1, dtype=torch.int32, device=device)
+    packed, table16 = field.field_weights(model.xyz_encoder.params, model.rgb_net.params, model.rgb_width)
+    call("mfnerf_render_test_fused", ptr(rays_o), ptr(rays_d), int(N_rays), ptr(model.center), ptr(model.half_size),
+         ptr(model.density_bitfield), int(model.cascades), float(model.scale), float(exp_step_factor),
+         int(model.grid_size), MAX_SAMPLES, int(kwargs.get("max_samples", MAX_SAMPLES)),
+         float(kwargs.get("T_threshold", 1e-4)), float(model._x_min), float(model._x_range), model.desc,
+         ptr(table16), ptr(packed), int(model.rgb_width), ptr(queue), ptr(opacity), ptr(depth), ptr(rgb),
+         ptr(samples), ptr(total_samples), stream())
+
+    rgb_bg = torch.ones(3, device=device) if exp_step_factor == 0 else torch.zeros(3, device=device)
+    rgb += rgb_bg * rearrange(1 - opacity, "n -> n 1")
+    results = {"opacity": opacity, "depth": depth, "rgb": rgb, "total_samples": total_samples, "samples": samples}
+    for k, v in results.items():
+        if kwargs.get("to_cpu", False):
+            v = v.cpu()
+            if kwargs.get("to_numpy", False):
+                v = v.numpy()
+        results[k] = v
+    return results
+
+
 def _render_rays_train(model, rays_o, rays_d, hits_t, **kwargs):
     """rendering.py:121-163."""
     exp_step_factor = kwargs.get("exp_step_factor", 0.0)

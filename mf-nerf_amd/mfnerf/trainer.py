@@ -172,21 +172,22 @@ class Trainer:
         m.density_bitfield.copy_(st.bitfield)
 
     @torch.no_grad()
-    def evaluate(self, images, poses, directions, chunk=None):
+    def evaluate(self, images, poses, directions, chunk=None, fused=False):
         """Mean test PSNR over views (train.py:197-206): the test-time renderer (rendering.py:46-118)
-        on every pixel of each (images[i], poses[i]) view; also returns the per-view values."""
+        on every pixel of each (images[i], poses[i]) view; also returns the per-view values.
+        fused=True renders with the single-launch kernel (rendering.render_fused) instead of the loop."""
         from .data import get_rays
-        from .rendering import render
+        from .rendering import render, render_fused
         model = self.to_ngp()
         dev = self.step.dev
         dirs = directions.to(dev)
         vals = []
         for img, pose in zip(images, poses):
             o, d = get_rays(dirs, pose.to(dev))
-            kw = {"test_time": True}
+            kw = {} if fused else {"test_time": True}
             if self.hp.scale > 0.5:
                 kw["exp_step_factor"] = 1 / 256
-            res = render(model, o, d, **kw)
+            res = render_fused(model, o, d, **kw) if fused else render(model, o, d, **kw)
             vals.append(psnr(res["rgb"].float(), img.to(dev)))
         return sum(vals) / len(vals), vals
 

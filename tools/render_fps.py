@@ -6,7 +6,10 @@ steps with the fused trainer, then times mfnerf.rendering.render(test_time=True)
 progressive test-time loop (rendering.py:46-118) over raymarching_test / composite_test_fw -- on
 full 800x800 held-out views, and reports frames/s and PSNR.  One JSON line on stdout.
 
-    python tools/render_fps.py [--train-steps 2000] [--views 5]
+    python tools/render_fps.py [--train-steps 2000] [--views 5] [--fused]
+
+--fused also times mfnerf.rendering.render_fused (the single-launch kernel) on the same frames and
+adds its figures (fused_*) to the line.
 """
 import argparse
 import json
@@ -26,9 +29,10 @@ def main():
     ap.add_argument("--train-steps", type=int, default=2000)
     ap.add_argument("--views", type=int, default=5)
     ap.add_argument("--width", type=int, default=800)
+    ap.add_argument("--fused", action="store_true", help="also time render_fused on the same frames")
     args = ap.parse_args()
     from mfnerf import data, synthetic
-    from mfnerf.rendering import render
+    from mfnerf.rendering import render, render_fused
     from mfnerf.trainer import HParams, Trainer
 
     dev = torch.device("cuda:0")
@@ -48,6 +52,7 @@ def main():
     t_imgs, t_poses, _, _ = data.ball_scene_views(scene, args.views, W, focal, seed=11, device=dev)
     dd = dirs.to(dev)
     times, psnrs, samples = [], [], []
+    f_times, f_psnrs, f_samples = [], [], []
     with torch.no_grad():
         for i, (img, pose) in enumerate(zip(t_imgs, t_poses)):
             o, d = data.get_rays(dd, pose.to(dev))
@@ -59,10 +64,25 @@ def main():
                 times.append(time.time() - t)
             psnrs.append(float(-10 * torch.log10(((res["rgb"].float() - img) ** 2).mean())))
             samples.append(int(res["total_samples"]))
+            if args.fused:
+                torch.cuda.synchronize()
+                t = time.time()
+                res = render_fused(model, o, d)
+                torch.cuda.synchronize()
+                if i > 0 or args.views == 1:
+                    f_times.append(time.time() - t)
+                f_psnrs.append(float(-10 * torch.log10(((res["rgb"].float() - img) ** 2).mean())))
+                f_samples.append(int(res["total_samples"]))
     fps = len(times) / sum(times)
+    fused = {}
+    if args.fused:
+        f_fps = len(f_times) / sum(f_times)
+        fused = {"fused_fps": round(f_fps, 2), "fused_ms_per_frame": round(1e3 / f_fps, 2),
+                 "fused_psnr": round(sum(f_psnrs) / len(f_psnrs), 2),
+                 "fused_samples_per_ray": round(sum(f_samples) / len(f_samples) / (W * W), 2)}
     print(json.dumps({"metric": "test-time render frames/s (800x800)", "fps": round(fps, 2),
                       "ms_per_frame": round(1e3 / fps, 2), "psnr": round(sum(psnrs) / len(psnrs), 2),
-                      "samples_per_ray": round(sum(samples) / len(samples) / (W * W), 2),
+                      "samples_per_ray": round(sum(samples) / len(samples) / (W * W), 2), **fused,
                       "train_steps": args.train_steps, "train_s": round(train_s, 2), "views": args.views,
                       "reference": "36.20 FPS, RTX 2080 Ti, Lego (README.md:123)",
                       "data": "analytic 12-ball scene, Lego intrinsics (no dataset in the image)"}), flush=True)
