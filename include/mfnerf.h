@@ -193,6 +193,29 @@ int mfnerf_grid_encode_fw_planar(const float* x, int64_t n, const int32_t* n_dev
                                  const mfnerf_grid_desc* desc, const void* table_f16, void* out_planes,
                                  int64_t plane_stride, mfnerf_stream_t stream);
 
+/* The encoding's gradient with respect to the points (tcnn's input gradient, Linear interpolation):
+ * dL_dout (n, n_levels*F) f32 row-major (as mfnerf_field_bw writes dL_dfeat) -> dL_dx (n,3) f32 in
+ * the units of x (the 1/x_range of the normalisation included); x, n, n_dev, x_min, x_range, desc and
+ * table_f16 as mfnerf_grid_encode_fw (the fp16 table the forward read).  fp32 accumulation in a
+ * fixed order (no atomics): the same bits on every run.  Rows at or past min(n, *n_dev) are left
+ * untouched. */
+int mfnerf_grid_encode_bw_input(const float* x, int64_t n, const int32_t* n_dev, float x_min, float x_range,
+                                const mfnerf_grid_desc* desc, const void* table_f16, const float* dL_dout,
+                                float* dL_dx, mfnerf_stream_t stream);
+
+/* mfnerf_grid_encode_bw_input reduced per ray (the backward of the ray march,
+ * custom_functions.py:103-112, without the per-sample gradient in memory): for each row r of rays_a
+ * (n_rays,3) i64 = (ray, first sample, samples), over the samples s of its segment of xyzs (n_samples,3),
+ * ts (n_samples), dL_dfeat (n_samples, n_levels*F), dL_ddirs (n_samples,3):
+ *     dL_drays_o[ray] = sum_s dL/dxyz_s,   dL_drays_d[ray] = sum_s (ts_s * dL/dxyz_s + dL_ddirs_s)
+ * (both (n_rays,3) f32; a ray without samples gets zeros; a segment is clamped to n_samples).  One
+ * wave per ray, a fixed summation order, no atomics: deterministic.  No allocation and no host read,
+ * so it is legal inside stream capture. */
+int mfnerf_rays_input_grad(const float* xyzs, const float* ts, const float* dL_dfeat, const float* dL_ddirs,
+                           const int64_t* rays_a, int64_t n_rays, int64_t n_samples, float x_min, float x_range,
+                           const mfnerf_grid_desc* desc, const void* table_f16, float* dL_drays_o,
+                           float* dL_drays_d, mfnerf_stream_t stream);
+
 /* Scatter dL/dout (n, n_levels*F) f32 into grad_table (n_entries*F) f32.  workspace (optional,
  * mfnerf_grid_encode_bw_workspace() bytes, ZERO on the first call; the call leaves it zero again):
  * private copies of the dense coarse levels' gradient, which spread their hot-line atomics.
@@ -373,6 +396,18 @@ int mfnerf_field_bw(const void* feat_f16, int64_t feat_plane_stride, const float
                     int rgb_width, const float* dL_dsigma, const float* dL_drgb, float grad_scale, float* dL_dfeat,
                     float* grad_xyz, float* grad_rgb, void* workspace, mfnerf_amp_state* amp, float* level_l1,
                     mfnerf_stream_t stream);
+
+/* mfnerf_field_bw plus the gradient with respect to the view directions: dL_ddirs (n,3) f32, rows
+ * below min(n, *n_dev) written.  dL/dSH is rows 0..15 of the product d[SH;h] = Wr1^T dR1 the
+ * backward forms anyway (fp16 operands, fp32 accumulation, the loss scale removed); the chain rule
+ * through SH4 and the normalisation d/|d| is fp32, the forward's fp16 rounding of SH taken as the
+ * identity.  Every other output is bit-identical to mfnerf_field_bw's, the deferred fold included;
+ * a non-finite dL_ddirs raises amp->nonfinite as well.  With mfnerf_grid_encode_bw_input this is
+ * tcnn's input gradient of the field (camera-pose refinement, train.py:91-94). */
+int mfnerf_field_bw_inputs(const void* feat_f16, int64_t feat_plane_stride, const float* dirs, int64_t n, const int32_t* n_dev, const void* packed,
+                           int rgb_width, const float* dL_dsigma, const float* dL_drgb, float grad_scale, float* dL_dfeat,
+                           float* grad_xyz, float* grad_rgb, void* workspace, mfnerf_amp_state* amp, float* level_l1,
+                           float* dL_ddirs, mfnerf_stream_t stream);
 
 /* grad_xyz = grad_rgb = NULL in mfnerf_field_bw defers the weight-gradient fold: the per-block
  * partial sums stay in workspace (dL_dfeat, level_l1 and the data-gradient part of the non-finite

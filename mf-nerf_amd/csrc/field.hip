@@ -289,6 +289,49 @@ __device__ __forceinline__ void dw_add32(float* img, const f32x16& a, int ot, in
 // one dW tile += dY x X into its register accumulator
 __device__ __forceinline__ void acc_tile(f32x16& reg, const SOp& dy, const SOp& x) { dw_acc_agpr(reg, dy, x); }
 
+// dL/dd of one sample from dL/dSH (mfnerf_field_bw_inputs).  dsh is the 32-row accumulator of
+// d[SH;h] = Wr1^T dR1, still scaled by the loss scale: register i < 8 of lane half h is SH row
+// (i&3) + 8(i>>2) + 4h, so h = 0 holds rows {0..3, 8..11} and h = 1 rows {4..7, 12..15} of the
+// sample lane&31.  Each half applies its own eight rows of the SH4 Jacobian (J^T g, in dn = d/|d|;
+// the encoding's (dn+1)/2 and the SH's 2u-1 cancel, the fp16 rounding of SH counts as identity):
+// per register the Jacobian row is selected by h and folded into the running 3-vector at once, so
+// nothing but the 3-vector and the direction's products stays live.  ONE exchange with lane^32 adds
+// the two halves' partial 3-vectors (a + b on one side, b + a on the other: the same bits).  Then
+// the normalisation: dL/dd = (g - dn (dn . g)) / |d|.  All fp32.
+__device__ __forceinline__ void sh4_bw_dir(const f32x16& dsh, int h, float invS, const float* d, float* out) {
+    const float nrm = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+    const float x = d[0] / nrm, y = d[1] / nrm, z = d[2] / nrm;
+    const float xy = x * y, xz = x * z, yz = y * z, x2 = x * x, y2 = y * y, z2 = z * z;
+    constexpr float c1 = 0.48860251190291987f, c2 = 1.0925484305920792f, c3 = 0.94617469575755997f,
+                    c4 = 0.54627421529603959f, c5 = 0.59004358992664352f, c6 = 2.8906114426405538f,
+                    c7 = 0.45704579946446572f, c8 = 0.3731763325901154f, c9 = 1.4453057213202769f;
+    const float a = c7 * (1.0f - 5.0f * z2), b = 3.0f * c5 * (y2 - x2);
+    const bool hi = h != 0;
+    float gx = 0.0f, gy = 0.0f, gz = 0.0f;
+    // register i: the Jacobian row (d/dx, d/dy, d/dz) of SH row lo (h == 0) or lo + 4 (h == 1)
+    auto row = [&](int i, float lx, float ly, float lz, float hx, float hy, float hz) {
+        const float v = dsh[i] * invS;
+        gx += v * (hi ? hx : lx);
+        gy += v * (hi ? hy : ly);
+        gz += v * (hi ? hz : lz);
+    };
+    row(0, 0.0f, 0.0f, 0.0f, c2 * y, c2 * x, 0.0f);                                        // rows 0 | 4
+    row(1, 0.0f, -c1, 0.0f, 0.0f, -c2 * z, -c2 * y);                                       //      1 | 5
+    row(2, 0.0f, 0.0f, c1, 0.0f, 0.0f, 2.0f * c3 * z);                                     //      2 | 6
+    row(3, -c1, 0.0f, 0.0f, -c2 * z, 0.0f, -c2 * x);                                       //      3 | 7
+    row(4, 2.0f * c4 * x, -2.0f * c4 * y, 0.0f, 0.0f, 0.0f, c8 * (15.0f * z2 - 3.0f));     //      8 | 12
+    row(5, -6.0f * c5 * xy, b, 0.0f, a, 0.0f, -10.0f * c7 * xz);                           //      9 | 13
+    row(6, c6 * yz, c6 * xz, c6 * xy, 2.0f * c9 * xz, -2.0f * c9 * yz, c9 * (x2 - y2));    //     10 | 14
+    row(7, 0.0f, a, -10.0f * c7 * yz, b, 6.0f * c5 * xy, 0.0f);                            //     11 | 15
+    gx += __shfl_xor(gx, 32, 64);
+    gy += __shfl_xor(gy, 32, 64);
+    gz += __shfl_xor(gz, 32, 64);
+    const float t = x * gx + y * gy + z * gz;
+    out[0] = (gx - x * t) / nrm;
+    out[1] = (gy - y * t) / nrm;
+    out[2] = (gz - z * t) / nrm;
+}
+
 // ---------------------------------------------------------------- cooperative backward (W = 64)
 // The round 1-3 per-wave backward held all 12 weight-gradient tiles in each wave (192 accumulator registers + ~170
 // for the chain): one wave per SIMD, nothing hides the chain's dependencies (PMC: waiting 56 % of
@@ -308,12 +351,13 @@ constexpr int COOP_BLOCKS = 512;   // two workgroups per CU (persistent)
 constexpr size_t COOP_LDS = (size_t)Geo<64>::N * FRAG_HALFS * 2 + (size_t)4 * COOP_SLOTS * TILE_BYTES;
 static_assert(COOP_LDS <= 80 * 1024, "two cooperative workgroups per CU");
 
-template <bool PLANAR>
+template <bool PLANAR, bool DDIRS = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void field_bw_coop_kernel(
     const _Float16* __restrict__ feat, int64_t plane_stride, const float* __restrict__ dirs, int64_t n,
     const int32_t* __restrict__ n_dev, const _Float16* __restrict__ packed, const float* __restrict__ dL_dsigma,
     const float* __restrict__ dL_drgb, float grad_scale, const float* __restrict__ scale_dev,
-    float* __restrict__ dL_dfeat, float* __restrict__ slab, int32_t* __restrict__ nonfinite, float* __restrict__ level_l1) {
+    float* __restrict__ dL_dfeat, float* __restrict__ slab, int32_t* __restrict__ nonfinite, float* __restrict__ level_l1,
+    float* __restrict__ dL_ddirs) {
     constexpr int W = 64;
     using G = Geo<W>;
     constexpr int MT = G::MT;
@@ -438,6 +482,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void f
             const float dh0 = in.gs * S * __expf(fminf(fmaxf(T.h0, -15.0f), 15.0f));
             dsh[8] = h == 0 ? dsh[8] + dh0 : dsh[8];
             dhb = pack8<8, false>(dsh);
+            if constexpr (DDIRS) {  // rows 0..15 = dL/dSH: the chain rule to the sample's direction
+                // (the direction is read again: keeping the forward's copy live costs registers)
+                __builtin_amdgcn_sched_barrier(0);
+                const int64_t s = tile * 32 + r, sc = max<int64_t>(0, min<int64_t>(s, nn - 1));
+                const float dv[3] = {dirs[3 * sc], dirs[3 * sc + 1], dirs[3 * sc + 2]};
+                float gd[3];
+                sh4_bw_dir(dsh, h, invS, dv, gd);
+                if (h == 0 && s < nn) {
+                    bad |= !(isfinite(gd[0]) && isfinite(gd[1]) && isfinite(gd[2]));
+                    dL_ddirs[3 * s] = gd[0]; dL_ddirs[3 * s + 1] = gd[1]; dL_ddirs[3 * s + 2] = gd[2];
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
         }
         __syncthreads();
         {
@@ -576,12 +633,13 @@ constexpr int COOP128_SLOTS = 6;
 constexpr size_t COOP128_LDS = (size_t)Geo<128>::N * FRAG_HALFS * 2 + (size_t)4 * COOP128_SLOTS * TILE_BYTES;
 static_assert(COOP128_LDS <= 160 * 1024, "one cooperative W = 128 workgroup per CU");
 
-template <bool PLANAR>
+template <bool PLANAR, bool DDIRS = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) void field_bw_coop128_kernel(
     const _Float16* __restrict__ feat, int64_t plane_stride, const float* __restrict__ dirs, int64_t n,
     const int32_t* __restrict__ n_dev, const _Float16* __restrict__ packed, const float* __restrict__ dL_dsigma,
     const float* __restrict__ dL_drgb, float grad_scale, const float* __restrict__ scale_dev,
-    float* __restrict__ dL_dfeat, float* __restrict__ slab, int32_t* __restrict__ nonfinite, float* __restrict__ level_l1) {
+    float* __restrict__ dL_dfeat, float* __restrict__ slab, int32_t* __restrict__ nonfinite, float* __restrict__ level_l1,
+    float* __restrict__ dL_ddirs) {
     constexpr int W = 128;
     using G = Geo<W>;
     constexpr int MT = G::MT;
@@ -705,6 +763,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) void f
             const float dh0 = in.gs * S * __expf(fminf(fmaxf(T.h0, -15.0f), 15.0f));
             dsh[8] = h == 0 ? dsh[8] + dh0 : dsh[8];
             dhb = pack8<8, false>(dsh);
+            if constexpr (DDIRS) {  // rows 0..15 = dL/dSH: the chain rule to the sample's direction
+                // (the direction is read again: keeping the forward's copy live costs registers)
+                __builtin_amdgcn_sched_barrier(0);
+                const int64_t s = tile * 32 + r, sc = max<int64_t>(0, min<int64_t>(s, nn - 1));
+                const float dv[3] = {dirs[3 * sc], dirs[3 * sc + 1], dirs[3 * sc + 2]};
+                float gd[3];
+                sh4_bw_dir(dsh, h, invS, dv, gd);
+                if (h == 0 && s < nn) {
+                    bad |= !(isfinite(gd[0]) && isfinite(gd[1]) && isfinite(gd[2]));
+                    dL_ddirs[3 * s] = gd[0]; dL_ddirs[3 * s + 1] = gd[1]; dL_ddirs[3 * s + 2] = gd[2];
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
         }
         __syncthreads();
 #pragma unroll
@@ -918,14 +989,15 @@ void launch_fw(const void* feat, int64_t ps, const float* dirs, int64_t n, const
 
 // the cooperative backward of width W (its kernel pair, workgroups = slab rows, LDS), then the slab fold
 // (unless deferred: grad_xyz null, mfnerf_field_bw_reduce folds the slab later)
-template <int W>
+// DDIRS (mfnerf_field_bw_inputs): the kernels' direction-gradient instantiation, writing dL_ddirs
+template <int W, bool DDIRS = false>
 int launch_bw(const void* feat, int64_t ps, const float* dirs, int64_t n, const int32_t* n_dev, const void* packed,
               const float* dL_dsigma, const float* dL_drgb, float grad_scale, const float* scale_dev, float* dL_dfeat,
               float* grad_xyz, float* grad_rgb, void* workspace, int32_t* nonfinite, float* level_l1,
-              mfnerf_stream_t stream) {
-    using K = decltype(&field_bw_coop_kernel<false>);
-    constexpr K k0 = W == 64 ? field_bw_coop_kernel<false> : field_bw_coop128_kernel<false>;
-    constexpr K k1 = W == 64 ? field_bw_coop_kernel<true> : field_bw_coop128_kernel<true>;
+              mfnerf_stream_t stream, float* dL_ddirs = nullptr) {
+    using K = decltype(&field_bw_coop_kernel<false, DDIRS>);
+    constexpr K k0 = W == 64 ? field_bw_coop_kernel<false, DDIRS> : field_bw_coop128_kernel<false, DDIRS>;
+    constexpr K k1 = W == 64 ? field_bw_coop_kernel<true, DDIRS> : field_bw_coop128_kernel<true, DDIRS>;
     constexpr size_t lds = W == 64 ? COOP_LDS : COOP128_LDS;
     const int rows = bw_rows(W);
     static const hipError_t attr = [] {
@@ -941,11 +1013,42 @@ int launch_bw(const void* feat, int64_t ps, const float* dirs, int64_t n, const 
     }
     hipLaunchKernelGGL(ps > 0 ? k1 : k0, dim3(rows), dim3(256), lds, stream, (const _Float16*)feat, ps, dirs, n,
                        n_dev, (const _Float16*)packed, dL_dsigma, dL_drgb, grad_scale, scale_dev, dL_dfeat,
-                       (float*)workspace, nonfinite, level_l1);
+                       (float*)workspace, nonfinite, level_l1, dL_ddirs);
     if (grad_xyz)
         hipLaunchKernelGGL(slab_reduce_kernel<W>, dim3((Geo<W>::N_DW + 63) / 64), dim3(256), 0, stream,
                            (const float*)workspace, rows, grad_xyz, grad_rgb, nonfinite, 0);
     return MFN_OK;
+}
+
+// mfnerf_field_bw (DDIRS off) and mfnerf_field_bw_inputs (on): the same checks and launches
+template <bool DDIRS>
+int field_bw_impl(const void* feat_f16, int64_t feat_plane_stride, const float* dirs, int64_t n, const int32_t* n_dev,
+                  const void* packed, int rgb_width, const float* dL_dsigma, const float* dL_drgb, float grad_scale,
+                  float* dL_dfeat, float* grad_xyz, float* grad_rgb, void* workspace, mfnerf_amp_state* amp,
+                  float* level_l1, mfnerf_stream_t stream, float* dL_ddirs) {
+    if (!width_ok(rgb_width)) return bad_width(rgb_width);
+    if (n < 0 || !(grad_scale >= 0.0f) || (grad_scale == 0.0f && !amp) ||
+        (feat_plane_stride != 0 && feat_plane_stride < n)) {
+        mfn_set_error("field_bw: bad size, plane stride or grad_scale (0 = dynamic needs amp)"); return MFN_ERR_INVALID;
+    }
+    if (n == 0) return MFN_OK;
+    if (!feat_f16 || !dirs || !packed || !dL_dsigma || !dL_drgb || !dL_dfeat || !workspace || (!grad_xyz != !grad_rgb) ||
+        (DDIRS && !dL_ddirs)) {
+        mfn_set_error("field_bw: null pointer"); return MFN_ERR_INVALID;
+    }
+    int32_t* nonfinite = amp ? &amp->nonfinite : nullptr;
+    const float* scale_dev = grad_scale == 0.0f ? &amp->scale : nullptr;
+    int st;
+    if (rgb_width == 128)
+        st = launch_bw<128, DDIRS>(feat_f16, feat_plane_stride, dirs, n, n_dev, packed, dL_dsigma, dL_drgb, grad_scale,
+                                   scale_dev, dL_dfeat, grad_xyz, grad_rgb, workspace, nonfinite, level_l1, stream,
+                                   dL_ddirs);
+    else
+        st = launch_bw<64, DDIRS>(feat_f16, feat_plane_stride, dirs, n, n_dev, packed, dL_dsigma, dL_drgb, grad_scale,
+                                  scale_dev, dL_dfeat, grad_xyz, grad_rgb, workspace, nonfinite, level_l1, stream,
+                                  dL_ddirs);
+    if (st != MFN_OK) return st;
+    return mfn_check_launch(DDIRS ? "field_bw_inputs" : "field_bw");
 }
 
 }  // namespace
@@ -1034,26 +1137,17 @@ int mfnerf_field_bw(const void* feat_f16, int64_t feat_plane_stride, const float
                     int rgb_width, const float* dL_dsigma, const float* dL_drgb, float grad_scale, float* dL_dfeat,
                     float* grad_xyz, float* grad_rgb, void* workspace, mfnerf_amp_state* amp, float* level_l1,
                     mfnerf_stream_t stream) {
-    if (!width_ok(rgb_width)) return bad_width(rgb_width);
-    if (n < 0 || !(grad_scale >= 0.0f) || (grad_scale == 0.0f && !amp) ||
-        (feat_plane_stride != 0 && feat_plane_stride < n)) {
-        mfn_set_error("field_bw: bad size, plane stride or grad_scale (0 = dynamic needs amp)"); return MFN_ERR_INVALID;
-    }
-    if (n == 0) return MFN_OK;
-    if (!feat_f16 || !dirs || !packed || !dL_dsigma || !dL_drgb || !dL_dfeat || !workspace || (!grad_xyz != !grad_rgb)) {
-        mfn_set_error("field_bw: null pointer"); return MFN_ERR_INVALID;
-    }
-    int32_t* nonfinite = amp ? &amp->nonfinite : nullptr;
-    const float* scale_dev = grad_scale == 0.0f ? &amp->scale : nullptr;
-    int st;
-    if (rgb_width == 128)
-        st = launch_bw<128>(feat_f16, feat_plane_stride, dirs, n, n_dev, packed, dL_dsigma, dL_drgb, grad_scale,
-                               scale_dev, dL_dfeat, grad_xyz, grad_rgb, workspace, nonfinite, level_l1, stream);
-    else
-        st = launch_bw<64>(feat_f16, feat_plane_stride, dirs, n, n_dev, packed, dL_dsigma, dL_drgb, grad_scale,
-                              scale_dev, dL_dfeat, grad_xyz, grad_rgb, workspace, nonfinite, level_l1, stream);
-    if (st != MFN_OK) return st;
-    return mfn_check_launch("field_bw");
+    return field_bw_impl<false>(feat_f16, feat_plane_stride, dirs, n, n_dev, packed, rgb_width, dL_dsigma, dL_drgb,
+                                grad_scale, dL_dfeat, grad_xyz, grad_rgb, workspace, amp, level_l1, stream, nullptr);
+}
+
+int mfnerf_field_bw_inputs(const void* feat_f16, int64_t feat_plane_stride, const float* dirs, int64_t n,
+                           const int32_t* n_dev, const void* packed,
+                           int rgb_width, const float* dL_dsigma, const float* dL_drgb, float grad_scale, float* dL_dfeat,
+                           float* grad_xyz, float* grad_rgb, void* workspace, mfnerf_amp_state* amp, float* level_l1,
+                           float* dL_ddirs, mfnerf_stream_t stream) {
+    return field_bw_impl<true>(feat_f16, feat_plane_stride, dirs, n, n_dev, packed, rgb_width, dL_dsigma, dL_drgb,
+                               grad_scale, dL_dfeat, grad_xyz, grad_rgb, workspace, amp, level_l1, stream, dL_ddirs);
 }
 
 static int field_bw_fold(int rgb_width, const void* workspace, float* grad_xyz, float* grad_rgb, int32_t* nonfinite,

@@ -2037,6 +2037,9 @@ int64_t binned_workspace_layout(const mfnerf_grid_desc* d, int64_t n_max, char* 
 
 }  // namespace
 
+// the layout limits of every grid kernel, for the other translation units (input_grad.hip)
+int mfn_check_grid_desc(const mfnerf_grid_desc* d, const char* what) { return check_desc(d, what); }
+
 extern "C" {
 
 int mfnerf_grid_encode_fw(const float* x, int64_t n, const int32_t* n_dev, float x_min, float x_range,

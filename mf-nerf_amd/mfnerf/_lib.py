@@ -96,7 +96,10 @@ SIGNATURES = {
     "mfnerf_field_bw_workspace": (_I64, [_I64, _I]),
     "mfnerf_field_bw_slab_rows": (_I, [_I]),
     "mfnerf_field_bw": (_I, [_P, _I64, _P, _I64, _P, _P, _I, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P]),
-    "mfnerf_occupancy_workspace": (_I64, [_I, _I]),
+    "mfnerf_field_bw_inputs": (_I, [_P, _I64, _P, _I64, _P, _P, _I, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mfnerf_grid_encode_bw_input": (_I, [_P, _I64, _P, _F, _F, ctypes.POINTER(GridDesc), _P, _P, _P, _P]),
+    "mfnerf_rays_input_grad": (_I, [_P, _P, _P, _P, _P, _I64, _I64, _F, _F, ctypes.POINTER(GridDesc), _P, _P, _P, _P]),
+    "mfnerf_occupancy_workspace":(_I64, [_I, _I]),
     "mfnerf_occupancy_points": (_I64, [_I, _I, _I64, _I]),
     "mfnerf_occupancy_cells": (_I, [_P, _I, _I, _F, _I64, _I, _F, ctypes.c_uint64, ctypes.c_uint64, _P, _P, _P, _P]),
     "mfnerf_occupancy_cells_dev": (_I, [_P, _I, _I, _F, _I64, _I, _F, ctypes.c_uint64, _P, _P, _P, _P, _P]),

@@ -20,8 +20,12 @@ class RayAABBIntersector(torch.autograd.Function):
     @staticmethod
     def forward(ctx, rays_o, rays_d, center, half_size, max_hits):
         rays_o, rays_d, center, half_size = _f32(rays_o, rays_d, center, half_size)
-        return tuple(vren.ray_aabb_intersect(rays_o.contiguous(), rays_d.contiguous(), center.contiguous(),
+        outs = tuple(vren.ray_aabb_intersect(rays_o.contiguous(), rays_d.contiguous(), center.contiguous(),
                                              half_size.contiguous(), max_hits))
+        # the hit interval is a constant of the march (no backward here or in the reference): rays
+        # that require a gradient (pose refinement) must not route one through it
+        ctx.mark_non_differentiable(*outs)
+        return outs
 
 
 class RayMarcher(torch.autograd.Function):

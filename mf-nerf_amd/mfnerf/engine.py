@@ -71,6 +71,10 @@ class StepConfig:
     # (the first steps, before the occupancy grid is pruned) overflows slots, whose extra records
     # are added by integer atomics (same sums, slower)
     bin_samples_per_ray: int = 128
+    # the loss gradient with respect to the batch's rays (camera-pose refinement, train.py:91-94):
+    # each part then carries dL_drays_o / dL_drays_d (Np,3), the unscaled gradient of the step's
+    # loss, valid after run() and after a replay.  Off: the same launches as without the option
+    ray_grads: bool = False
 
 
 @dataclass
@@ -240,6 +244,10 @@ class TrainStep:
         t.drgb_s = torch.empty(cap, 3, **f32)
         t.dfeat = torch.empty(cap, c.L * c.F, **f32)
         t.field_ws = torch.empty(load().mfnerf_field_bw_workspace(cap, c.rgb_width) // 4, **f32)
+        if c.ray_grads:
+            t.ddirs = torch.empty(cap, 3, **f32)
+            t.dL_drays_o = torch.zeros(Np, 3, **f32)
+            t.dL_drays_d = torch.zeros(Np, 3, **f32)
         if self._binned():
             nb = load().mfnerf_grid_encode_bw_binned_workspace(self.desc, self._bin_slots())
         else:
@@ -441,13 +449,22 @@ class TrainStep:
                  ptr(t.sigma), ptr(t.rgb_s), ptr(t.ws), ptr(m.deltas), ptr(m.ts), ptr(m.rays_a), ptr(t.opacity),
                  ptr(t.depth), ptr(t.rgb), Np, cap, c.T_threshold, ptr(t.dsig), ptr(t.drgb_s), s)
             mark("composite_bw")
-        call("mfnerf_field_bw", ptr(t.feat), cap, ptr(m.dirs), cap, ptr(m.counter), ptr(self.packed), c.rgb_width,
-             ptr(t.dsig), ptr(t.drgb_s), 0.0 if c.dynamic_loss_scale else self.grad_scale, ptr(t.dfeat),
-             None if store_fold else ptr(t.mlp_grad),
-             None if store_fold else ptr(t.mlp_grad[self.off_rgb:]),
-             ptr(t.field_ws),
-             self._amp_ptr(),
-             ptr(self._level_l1) if self._fixed() else None, s)
+        bw_args = (ptr(t.feat), cap, ptr(m.dirs), cap, ptr(m.counter), ptr(self.packed), c.rgb_width,
+                   ptr(t.dsig), ptr(t.drgb_s), 0.0 if c.dynamic_loss_scale else self.grad_scale, ptr(t.dfeat),
+                   None if store_fold else ptr(t.mlp_grad),
+                   None if store_fold else ptr(t.mlp_grad[self.off_rgb:]),
+                   ptr(t.field_ws),
+                   self._amp_ptr(),
+                   ptr(self._level_l1) if self._fixed() else None)
+        if c.ray_grads:
+            # the same backward plus dL/ddirs, then dL/dxyz through the encoding summed per ray
+            # (the table is the fp16 copy the forward gathered from: Adam comes later in the step)
+            call("mfnerf_field_bw_inputs", *bw_args, ptr(t.ddirs), s)
+            call("mfnerf_rays_input_grad", ptr(m.xyzs), ptr(m.ts), ptr(t.dfeat), ptr(t.ddirs), ptr(m.rays_a), Np, cap,
+                 self.x_min, self.x_range, self.desc, ptr(self.p16[self.off_table:]), ptr(t.dL_drays_o),
+                 ptr(t.dL_drays_d), s)
+        else:
+            call("mfnerf_field_bw", *bw_args, s)
         if store_fold:  # the fold writes the MLPs' gradient outright (nothing zeroed it)
             call("mfnerf_field_bw_reduce_store", c.rgb_width, ptr(t.field_ws), ptr(t.mlp_grad),
                  ptr(t.mlp_grad[self.off_rgb:]), self._amp_ptr(), s)

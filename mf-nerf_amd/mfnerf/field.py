@@ -28,6 +28,30 @@ def grid_encode_fw(x, n, table16, layout, desc, x_min=0.0, x_range=1.0, n_dev=No
     return out
 
 
+def grid_encode_bw_input(x, n, table16, dL_dout, desc, x_min=0.0, x_range=1.0, n_dev=None, out=None):
+    """dL/dx (n,3) f32 of the encoding at x from dL/dout (n, L*F) f32: tcnn's input gradient (rows
+    beyond *n_dev untouched).  table16: the fp16 table the forward read."""
+    if out is None:
+        out = torch.empty(n, 3, dtype=torch.float32, device=x.device)
+    call("mfnerf_grid_encode_bw_input", ptr(x), int(n), ptr(n_dev), float(x_min), float(x_range), desc, ptr(table16),
+         ptr(dL_dout), ptr(out), stream())
+    return out
+
+
+def rays_input_grad(xyzs, ts, dL_dfeat, dL_ddirs, rays_a, table16, desc, x_min=0.0, x_range=1.0, out_o=None,
+                    out_d=None):
+    """(dL/drays_o, dL/drays_d), each (R,3) f32: grid_encode_bw_input reduced over each ray's samples
+    (RayMarcher.backward without the per-sample gradient in memory); deterministic."""
+    R = rays_a.shape[0]
+    if out_o is None:
+        out_o = torch.empty(R, 3, dtype=torch.float32, device=rays_a.device)
+    if out_d is None:
+        out_d = torch.empty(R, 3, dtype=torch.float32, device=rays_a.device)
+    call("mfnerf_rays_input_grad", ptr(xyzs), ptr(ts), ptr(dL_dfeat), ptr(dL_ddirs), ptr(rays_a), int(R),
+         int(ts.shape[0]), float(x_min), float(x_range), desc, ptr(table16), ptr(out_o), ptr(out_d), stream())
+    return out_o, out_d
+
+
 def grid_bw_workspace(desc, device):
     """Zeroed private-copy workspace for grid_encode_bw (stays zero between calls)."""
     nb = load().mfnerf_grid_encode_bw_workspace(desc)
@@ -94,6 +118,14 @@ def field_bw(feat, dirs, n, packed, dL_dsigma, dL_drgb, grad_scale, dL_dfeat, gr
          ptr(nonfinite), None, stream())
 
 
+def field_bw_inputs(feat, dirs, n, packed, dL_dsigma, dL_drgb, grad_scale, dL_dfeat, grad_xyz_net, grad_rgb, workspace,
+                    dL_ddirs, rgb_width=64, n_dev=None, nonfinite=None):
+    """field_bw that also writes dL_ddirs (n,3) f32, the gradient with respect to the directions."""
+    call("mfnerf_field_bw_inputs", ptr(feat), 0, ptr(dirs), int(n), ptr(n_dev), ptr(packed), int(rgb_width),
+         ptr(dL_dsigma), ptr(dL_drgb), float(grad_scale), ptr(dL_dfeat), ptr(grad_xyz_net), ptr(grad_rgb),
+         ptr(workspace), ptr(nonfinite), None, ptr(dL_ddirs), stream())
+
+
 def pow2_grad_scale(max_abs):
     """Largest power of two keeping the largest incoming grad <= ~1 in the fp16 backward."""
     if not (max_abs > 0) or not math.isfinite(max_abs):
@@ -117,19 +149,30 @@ class GridEncodeFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, table, layout, desc):
+        ctx.x_dtype = x.dtype
         x = x.float().contiguous()
-        feat = grid_encode_fw(x, x.shape[0], table.detach().half().contiguous(), layout, desc)
-        ctx.save_for_backward(x)
+        table16 = table.detach().half().contiguous()
+        feat = grid_encode_fw(x, x.shape[0], table16, layout, desc)
+        # the fp16 table is kept for the backward only when x wants a gradient (tcnn's input gradient)
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(x, table16)
+        else:
+            ctx.save_for_backward(x)
         ctx.layout, ctx.desc, ctx.n_table = layout, desc, table.numel()
         return feat
 
     @staticmethod
     def backward(ctx, dL_dfeat):
-        (x,) = ctx.saved_tensors
-        g = torch.zeros(ctx.n_table, dtype=torch.float32, device=x.device)
-        grid_encode_bw(x, x.shape[0], dL_dfeat.float().contiguous(), g, ctx.layout, ctx.desc,
-                       workspace=_grid_ws(ctx.desc, x.device))
-        return None, g, None, None
+        x = ctx.saved_tensors[0]
+        dfeat = dL_dfeat.float().contiguous()
+        g = None
+        if ctx.needs_input_grad[1]:
+            g = torch.zeros(ctx.n_table, dtype=torch.float32, device=x.device)
+            grid_encode_bw(x, x.shape[0], dfeat, g, ctx.layout, ctx.desc, workspace=_grid_ws(ctx.desc, x.device))
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = grid_encode_bw_input(x, x.shape[0], ctx.saved_tensors[1], dfeat, ctx.desc).to(ctx.x_dtype)
+        return dx, g, None, None
 
 
 _weights_cache = {}
@@ -163,19 +206,25 @@ class NGPFieldFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xyzs, dirs, xyz_params, rgb_params, layout, desc, x_min, x_range, rgb_width):
+        ctx.in_dtypes = (xyzs.dtype, dirs.dtype)
         xyzs = xyzs.float().contiguous()
         dirs = dirs.float().contiguous()
         n = xyzs.shape[0]
         packed, table16 = field_weights(xyz_params, rgb_params, rgb_width)
         feat = grid_encode_fw(xyzs, n, table16, layout, desc, x_min, x_range)
         sigma, rgb = field_fw(feat, dirs, n, packed, rgb_width)
-        ctx.save_for_backward(xyzs, dirs, feat, packed, sigma)
+        # input gradients (rays that require one: pose refinement) read the fp16 table again
+        ctx.input_grads = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        if ctx.input_grads:
+            ctx.save_for_backward(xyzs, dirs, feat, packed, sigma, table16)
+        else:
+            ctx.save_for_backward(xyzs, dirs, feat, packed, sigma)
         ctx.cfg = (layout, desc, x_min, x_range, rgb_width, xyz_params.numel(), rgb_params.numel())
         return sigma, rgb
 
     @staticmethod
     def backward(ctx, dL_dsigma, dL_drgb):
-        xyzs, dirs, feat, packed, sigma = ctx.saved_tensors
+        xyzs, dirs, feat, packed, sigma = ctx.saved_tensors[:5]
         layout, desc, x_min, x_range, rgb_width, n_xyz, n_rgb = ctx.cfg
         n = xyzs.shape[0]
         dev = xyzs.device
@@ -190,10 +239,20 @@ class NGPFieldFunction(torch.autograd.Function):
         g_rgb = torch.zeros(n_rgb, dtype=torch.float32, device=dev)
         dfeat = torch.empty(n, layout.L * layout.F, dtype=torch.float32, device=dev)
         ws = field_bw_workspace(n, rgb_width, dev)
-        field_bw(feat, dirs, n, packed, dsig, drgb, S, dfeat, g_xyz[:XYZ_NET_PARAMS], g_rgb, ws, rgb_width)
+        d_xyzs = d_dirs = None
+        if ctx.input_grads:
+            d_dirs = torch.empty(n, 3, dtype=torch.float32, device=dev)
+            field_bw_inputs(feat, dirs, n, packed, dsig, drgb, S, dfeat, g_xyz[:XYZ_NET_PARAMS], g_rgb, ws, d_dirs,
+                            rgb_width)
+            if ctx.needs_input_grad[0]:
+                d_xyzs = grid_encode_bw_input(xyzs, n, ctx.saved_tensors[5], dfeat, desc, x_min, x_range)
+                d_xyzs = d_xyzs.to(ctx.in_dtypes[0])
+            d_dirs = d_dirs.to(ctx.in_dtypes[1]) if ctx.needs_input_grad[1] else None
+        else:
+            field_bw(feat, dirs, n, packed, dsig, drgb, S, dfeat, g_xyz[:XYZ_NET_PARAMS], g_rgb, ws, rgb_width)
         grid_encode_bw(xyzs, n, dfeat, g_xyz[XYZ_NET_PARAMS:], layout, desc, x_min, x_range,
                        workspace=_grid_ws(desc, dev))
-        return None, None, g_xyz, g_rgb, None, None, None, None, None
+        return d_xyzs, d_dirs, g_xyz, g_rgb, None, None, None, None, None
 
 
 class NGPDensityFunction(torch.autograd.Function):
