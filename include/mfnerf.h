@@ -525,6 +525,53 @@ int mfnerf_sample_rays_prep(const float* images, const float* poses, const float
                             const float* center, const float* half_size, float near, float* hits_t, float* noise,
                             mfnerf_stream_t stream);
 
+/* mfnerf_sample_rays_prep that also returns the draws: img_idx / pix_idx (n_rays) i32 (optional), the
+ * image and pixel of every ray, which the pose gradient needs (train.py:91-94).  The same kernel: for
+ * the same seed and call counter the same draws and the same bits as mfnerf_sample_rays_prep, and
+ * the indices of mfnerf_sample_rays. */
+int mfnerf_sample_rays_prep_idx(const float* images, const float* poses, const float* directions, int64_t n_img,
+                                int64_t hw, int64_t n_rays, int same_image, uint64_t seed, uint64_t* call, float* out,
+                                const float* center, const float* half_size, float near, float* hits_t, float* noise,
+                                int32_t* img_idx, int32_t* pix_idx, mfnerf_stream_t stream);
+
+/* ---------------------------------------------------------------- camera-pose refinement */
+
+/* The reference's --optimize_ext (train.py:91-94, 122-139; datasets/ray_utils.py axisangle_to_R): image
+ * i has a rotation offset dR[i] (axis-angle) and a translation offset dT[i]; its refined pose is
+ * [R(dR[i]) @ R0[i] | t0[i] + dT[i]], R(w) = I + sin(t)/t K + (1 - cos t)/t^2 K^2, t = |w| + 1e-7, fp32.
+ * A ray of image i and pixel p has rays_d = R(dR[i]) u, u = R0[i] @ directions[p], rays_o = t0[i] + dT[i].
+ *
+ * mfnerf_pose_grad: the batch's ray gradients reduced per image,
+ *     grad_dT[i] = sum_r dL_drays_o[r],   grad_dR[i] = sum_r J(dR[i], u_r)^T dL_drays_d[r]
+ * over the rays r with img_idx[r] == i, J the Jacobian of w -> R(w) u for that formula, guard included
+ * (the gradient of |w| at 0 taken as 0: u x g there, as torch autograd gives); the derivatives of the
+ * two coefficients are evaluated by their series under t = 0.25, where the closed forms cancel.
+ * dL_drays_o / dL_drays_d (n_rays,3) f32, img_idx / pix_idx (n_rays) i32, poses (n_img,3,4) the BASE
+ * poses, directions (hw,3), dR (n_img,3); grad_dR / grad_dT (n_img,3) f32: every row is written (zeros
+ * for an image without a ray; a ray whose img_idx is outside [0, n_img) or pix_idx outside [0, hw)
+ * counts nowhere).  One workgroup per image, fixed summation order, no float atomics: the same bits
+ * on every run.  amp (optional): a non-finite output raises amp->nonfinite (never cleared here).  No
+ * allocation and no host read: legal inside stream capture. */
+int mfnerf_pose_grad(const float* dL_drays_o, const float* dL_drays_d, const int32_t* img_idx, const int32_t* pix_idx,
+                     const float* poses, const float* directions, const float* dR, int64_t n_rays, int64_t n_img,
+                     int64_t hw, float* grad_dR, float* grad_dT, mfnerf_amp_state* amp, mfnerf_stream_t stream);
+
+/* The pose optimizer (train.py:139: torch Adam over [dR, dT], betas 0.9/0.999, eps 1e-8, lr 1e-6) and
+ * the composition of the refined poses.  dR, dT (n_img,3) f32 updated in place from grad_dR / grad_dT;
+ * m, v (2,n_img,3) f32 = [dR's | dT's] moments; step_dev (device i32): completed pose steps, the
+ * update uses t = *step_dev + 1 (bias corrections 1 - beta^t) and then increments it; lr_dev (optional
+ * device f32) replaces lr.  Every row is updated (dense parameters: a zero gradient still decays the
+ * moments and moves the row).  Then poses_out (n_img,3,4) f32 = [R(dR[i]) @ R0[i] | t0[i] + dT[i]] from
+ * the base `poses` (poses_out != poses); with dR = dT = 0 it equals the base poses bit for bit.
+ * amp (optional): when amp->nonfinite != 0 on entry (raised by mfnerf_field_bw or mfnerf_pose_grad)
+ * dR, dT, m, v and step_dev stay untouched and poses_out is composed from the unchanged offsets;
+ * nothing of amp is written -- the field's optimizer pass stays the one place that counts the skip
+ * and runs GradScaler.update().  grad_dR == grad_dT == NULL: no update, the composition only. */
+int mfnerf_pose_step(float* dR, float* dT, float* m, float* v, const float* grad_dR, const float* grad_dT,
+                     const float* poses, int64_t n_img, float lr, float beta1, float beta2, float eps,
+                     int32_t* step_dev, const float* lr_dev, const mfnerf_amp_state* amp, float* poses_out,
+                     mfnerf_stream_t stream);
+
 /* ---------------------------------------------------------------- optimizer */
 
 /* Adam (apex FusedAdam semantics, adam_w_mode=False, no weight decay; train.py:136):

@@ -154,3 +154,23 @@ extern "C" int mfnerf_sample_rays_prep(const float* images, const float* poses, 
                        (int32_t*)nullptr, prep);
     return mfn_check_launch("sample_rays_prep");
 }
+
+extern "C" int mfnerf_sample_rays_prep_idx(const float* images, const float* poses, const float* directions,
+                                           int64_t n_img, int64_t hw, int64_t n_rays, int same_image, uint64_t seed,
+                                           uint64_t* call, float* out, const float* center, const float* half_size,
+                                           float near, float* hits_t, float* noise, int32_t* img_idx,
+                                           int32_t* pix_idx, mfnerf_stream_t stream) {
+    if (n_img <= 0 || hw <= 0 || n_rays < 0 || n_img > 0x7fffffff || hw > 0x7fffffff) {
+        mfn_set_error("sample_rays_prep_idx: bad sizes");
+        return MFN_ERR_INVALID;
+    }
+    if (n_rays == 0) return MFN_OK;
+    if (!images || !poses || !directions || !out || !center || !half_size || !hits_t || !noise) {
+        mfn_set_error("sample_rays_prep_idx: null pointer");
+        return MFN_ERR_INVALID;
+    }
+    const MarchPrep prep{center, half_size, near, hits_t, noise};
+    hipLaunchKernelGGL(sample_rays_kernel, dim3((unsigned)div_up<int64_t>(n_rays, 256)), dim3(256), 0, stream, images,
+                       poses, directions, n_img, hw, n_rays, same_image, seed, call, out, img_idx, pix_idx, prep);
+    return mfn_check_launch("sample_rays_prep_idx");
+}

@@ -112,6 +112,10 @@ SIGNATURES = {
     "mfnerf_sample_rays": (_I, [_P, _P, _P, _I64, _I64, _I64, _I, ctypes.c_uint64, _P, _P, _P, _P, _P]),
     "mfnerf_sample_rays_prep": (_I, [_P, _P, _P, _I64, _I64, _I64, _I, ctypes.c_uint64, _P, _P, _P, _P, _F, _P, _P,
                                      _P]),
+    "mfnerf_sample_rays_prep_idx": (_I, [_P, _P, _P, _I64, _I64, _I64, _I, ctypes.c_uint64, _P, _P, _P, _P, _F, _P,
+                                         _P, _P, _P, _P]),
+    "mfnerf_pose_grad": (_I, [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P]),
+    "mfnerf_pose_step": (_I, [_P, _P, _P, _P, _P, _P, _P, _I64, _F, _F, _F, _F, _P, _P, _P, _P, _P]),
     "mfnerf_adam_step": (_I, [_P, _P, _P, _P, _P, _I64, _F, _F, _F, _F, _F, _I, _P, _P, _P, _I, _P]),
     "mfnerf_adam_step_shard": (_I, [_P, _P, _P, _P, _P, _I64, _F, _F, _F, _F, _F, _P, _P, _P, _P, _I, _P]),
     "mfnerf_adam_step_fixed": (_I, [_P, _P, _P, _P, _P, _I64, _I64, ctypes.POINTER(GridDesc), _P, _P, _F, _F, _F, _F, _P, _P, _P, _P]),

@@ -302,18 +302,30 @@ class DeviceDataset:
 
     from_nsvf = from_dataset
 
-    def sample(self, out, img_idx=None, pix_idx=None, prep=None):
+    def sample(self, out, img_idx=None, pix_idx=None, prep=None, poses=None):
         """out (3, N, 3) f32 <- [rays_o | rays_d | rgb] of N random rays.  prep = (center, half_size,
         near, hits_t (N,2), noise (N)): also the march prologue (AABB hit, near clamp, noise) of the
-        drawn rays, in the same launch (mfnerf_sample_rays_prep)."""
+        drawn rays, in the same launch (mfnerf_sample_rays_prep; with img_idx / pix_idx (N) i32, which
+        receive the draws, mfnerf_sample_rays_prep_idx).  poses: a (n_img,3,4) f32 device buffer read
+        instead of self.poses (the refined poses of pose refinement)."""
         n = out.shape[1]
+        if poses is None:
+            poses = self.poses
+        elif (poses.shape != self.poses.shape or poses.dtype != torch.float32 or not poses.is_contiguous()
+              or poses.device != self.poses.device):
+            raise ValueError("poses= must be a contiguous float32 (n_img,3,4) tensor on the dataset's device")
         if prep is not None:
             center, half_size, near, hits_t, noise = prep
-            call("mfnerf_sample_rays_prep", ptr(self.images), ptr(self.poses), ptr(self.directions), self.n_img,
+            if img_idx is not None or pix_idx is not None:
+                call("mfnerf_sample_rays_prep_idx", ptr(self.images), ptr(poses), ptr(self.directions), self.n_img,
+                     self.hw, n, self.same_image, self.seed, ptr(self.calls), ptr(out), ptr(center), ptr(half_size),
+                     float(near), ptr(hits_t), ptr(noise), ptr(img_idx), ptr(pix_idx), stream())
+                return out
+            call("mfnerf_sample_rays_prep", ptr(self.images), ptr(poses), ptr(self.directions), self.n_img,
                  self.hw, n, self.same_image, self.seed, ptr(self.calls), ptr(out), ptr(center), ptr(half_size),
                  float(near), ptr(hits_t), ptr(noise), stream())
             return out
-        call("mfnerf_sample_rays", ptr(self.images), ptr(self.poses), ptr(self.directions), self.n_img, self.hw, n,
+        call("mfnerf_sample_rays", ptr(self.images), ptr(poses), ptr(self.directions), self.n_img, self.hw, n,
              self.same_image, self.seed, ptr(self.calls), ptr(out), ptr(img_idx), ptr(pix_idx), stream())
         return out
 

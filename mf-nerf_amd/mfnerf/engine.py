@@ -75,6 +75,16 @@ class StepConfig:
     # each part then carries dL_drays_o / dL_drays_d (Np,3), the unscaled gradient of the step's
     # loss, valid after run() and after a replay.  Off: the same launches as without the option
     ray_grads: bool = False
+    # camera-pose refinement inside the step (train.py:91-94, 122-139, --optimize_ext): per-image
+    # rotation / translation offsets trained by their own Adam (lr pose_lr) from the ray gradients,
+    # the batch drawn from the refined poses.  Implies ray_grads; needs an attached dataset, one part,
+    # no shard and no exchange.  Off: the same launches and buffers as without the option
+    refine_poses: bool = False
+    pose_lr: float = 1e-6
+
+    def __post_init__(self):
+        if self.refine_poses:
+            self.ray_grads = True
 
 
 @dataclass
@@ -121,6 +131,9 @@ class TrainStep:
         c = cfg
         if c.n_parts < 1 or c.n_rays % c.n_parts:
             raise ValueError(f"n_rays={c.n_rays} must split into n_parts={c.n_parts} equal parts")
+        if c.refine_poses and c.n_parts != 1:
+            raise ValueError(f"refine_poses needs n_parts == 1 (got {c.n_parts}): the pose gradient is reduced "
+                             "over the whole batch in one chain")
         self.cascades = max(1 + int(np.ceil(np.log2(2 * c.scale))), 1)
         self.G = 128
         b = float(np.exp(np.log(c.N_max * c.scale / c.N_min) / (c.L - 1)))
@@ -215,6 +228,66 @@ class TrainStep:
         self.dataset = ds
         self._sampled = _packed_batch(torch.zeros(3, self.cfg.n_rays, 3, device=self.dev))
         self.graphs = None
+        if self.cfg.refine_poses:
+            self._pose_buffers(ds)
+
+    # ---------------------------------------------------------------- pose refinement
+    def _pose_buffers(self, ds):
+        """The pose state (train.py:122-128: dR, dT zero) and its Adam moments, touched only on the
+        main stream, and one refined-pose buffer per march buffer set: the draw into set j reads
+        pose_buf[j], the step that trains on set j writes its updated composition back into it -- the
+        draw that read it is long done, the next one is two steps away and ordered by the replay's
+        events.  The next step's draw, which runs beside this step, reads the other buffer, so it never
+        reads what this step writes (and sees the updates one step late)."""
+        dev, n = self.dev, ds.n_img
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.dR = torch.zeros(n, 3, **f32)
+        self.dT = torch.zeros(n, 3, **f32)
+        self.pose_m = torch.zeros(2, n, 3, **f32)
+        self.pose_v = torch.zeros(2, n, 3, **f32)
+        self.pose_grad = torch.zeros(2, n, 3, **f32)  # grad_dR | grad_dT of the last step
+        self.pose_step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.pose_lr_dev = torch.full((1,), float(self.cfg.pose_lr), **f32)
+        self.pose_buf = [ds.poses.clone(), ds.poses.clone()]
+        for mb in self.mbuf:
+            self._pose_idx_buffers(mb)
+
+    def _pose_idx_buffers(self, mb):
+        mb.img_idx = torch.zeros(self.cfg.n_rays, dtype=torch.int32, device=self.dev)
+        mb.pix_idx = torch.zeros(self.cfg.n_rays, dtype=torch.int32, device=self.dev)
+
+    def _check_refine(self, exchange=None):
+        if not self.cfg.refine_poses:
+            return
+        if self.dataset is None:
+            raise ValueError("refine_poses needs an attached dataset (attach_dataset): the step draws its batch "
+                             "from the refined poses")
+        if self.shard is not None or exchange is not None:
+            raise ValueError("refine_poses does not run with a sharded optimizer or a gradient exchange: "
+                             "data-parallel pose refinement is out of scope")
+
+    def set_pose_lr(self, lr):
+        """The pose optimizer's device-resident learning rate."""
+        self.pose_lr_dev.fill_(float(lr))
+
+    def compose_poses(self):
+        """Both refined-pose buffers from the current dR / dT (no update).  Call with the side stream
+        idle (capture() and a checkpoint load do)."""
+        for buf in self.pose_buf:
+            call("mfnerf_pose_step", ptr(self.dR), ptr(self.dT), None, None, None, None, ptr(self.dataset.poses),
+                 self.dataset.n_img, 0.0, 0.9, 0.999, 1e-8, None, None, None, ptr(buf), stream())
+
+    def _pose_update(self, mb):
+        """After the ray gradients of the step on mb: the per-image reduction, the pose Adam step (skipped
+        with the field's on a non-finite gradient) and the refined poses into mb's pose buffer."""
+        ds, t = self.dataset, self.parts[0]
+        call("mfnerf_pose_grad", ptr(t.dL_drays_o), ptr(t.dL_drays_d), ptr(mb.img_idx), ptr(mb.pix_idx),
+             ptr(ds.poses), ptr(ds.directions), ptr(self.dR), self.cfg.n_rays, ds.n_img, ds.hw,
+             ptr(self.pose_grad[0]), ptr(self.pose_grad[1]), self._amp_ptr(), stream())
+        call("mfnerf_pose_step", ptr(self.dR), ptr(self.dT), ptr(self.pose_m), ptr(self.pose_v),
+             ptr(self.pose_grad[0]), ptr(self.pose_grad[1]), ptr(ds.poses), ds.n_img, float(self.cfg.pose_lr), 0.9,
+             0.999, 1e-8, ptr(self.pose_step_dev), ptr(self.pose_lr_dev), self._amp_ptr(),
+             ptr(self.pose_buf[self.mbuf.index(mb)]), stream())
 
     # ---------------------------------------------------------------- buffers
     def _part_buffers(self, q):
@@ -280,6 +353,8 @@ class TrainStep:
             ws_bytes = load().mfnerf_raymarching_train_workspace(self.Np, c.max_samples)
             t.march_ws = torch.empty(max(16, ws_bytes), dtype=torch.uint8, device=dev)
             m.part.append(t)
+        if c.refine_poses and getattr(self, "dataset", None) is not None:
+            self._pose_idx_buffers(m)
         return m
 
     def _use(self, mb):
@@ -354,6 +429,9 @@ class TrainStep:
         unless force (a one-rank process group running the sharded path, for tests)."""
         if world <= 1 and not force:
             return
+        if self.cfg.refine_poses:
+            raise ValueError("refine_poses does not run with a sharded optimizer: data-parallel pose refinement "
+                             "is out of scope")
         if self.n_alloc % (64 * world):
             raise ValueError(f"world size {world} does not divide the padded parameter count {self.n_alloc}")
         k = self.n_alloc // world
@@ -371,7 +449,12 @@ class TrainStep:
     def _draw(self, batch: Batch, mb):
         """The attached dataset's next batch into `batch`, with the march prologue (AABB + near clamp
         + noise) of mb in the same launch."""
-        self.dataset.sample(batch.buf, prep=(self.center, self.half_size, NEAR_DISTANCE, mb.hits, mb.noise))
+        prep = (self.center, self.half_size, NEAR_DISTANCE, mb.hits, mb.noise)
+        if self.cfg.refine_poses:
+            self.dataset.sample(batch.buf, prep=prep, img_idx=mb.img_idx, pix_idx=mb.pix_idx,
+                                poses=self.pose_buf[self.mbuf.index(mb)])
+        else:
+            self.dataset.sample(batch.buf, prep=prep)
 
     def _march(self, batch: Batch, mb, mark, prepped=False, noise=None):
         """AABB + near clamp + noise for the whole batch (unless _draw did it), then one ray march per
@@ -468,6 +551,8 @@ class TrainStep:
         if store_fold:  # the fold writes the MLPs' gradient outright (nothing zeroed it)
             call("mfnerf_field_bw_reduce_store", c.rgb_width, ptr(t.field_ws), ptr(t.mlp_grad),
                  ptr(t.mlp_grad[self.off_rgb:]), self._amp_ptr(), s)
+        if c.refine_poses:
+            self._pose_update(mb)
         mark("field_bw")
 
     def _fixed(self):
@@ -703,6 +788,10 @@ class TrainStep:
         optimize=False stops after the backward and leaves the step's gradient in self.grads (no
         Adam step, no repack; for inspection)."""
         mark = mark or (lambda name: None)
+        if self.cfg.refine_poses:
+            self._check_refine(exchange)
+            if batch is not None:
+                raise ValueError("refine_poses draws its batch from the attached dataset: pass no batch")
         self._flush_pack()
         mb = self.mbuf[0]
         prepped = batch is None
@@ -759,9 +848,12 @@ class TrainStep:
         drawn from the step's generator (parity tests driving several processes with one draw).
         Call after at least one eager step (lazy library init happens outside capture)."""
         N = self.cfg.n_rays
+        self._check_refine()
         self._flush_pack()
         if len(self.mbuf) == 1:
             self.mbuf.append(self._march_buffers())
+        if self.cfg.refine_poses:
+            self.compose_poses()  # both buffers start from the offsets the eager steps left
         self._static = [_packed_batch(torch.zeros(3, N, 3, device=self.dev)) for _ in range(2)]
         self._host_noise = bool(host_noise)
         self._static_noise = [torch.zeros(N, device=self.dev) for _ in range(2)] if host_noise else None
@@ -945,6 +1037,7 @@ class TrainStep:
         noise / next_noise: the perturbations of batch / next_batch (capture(host_noise=True))."""
         from . import dp
         g, j, P = self.graphs, self._parity, self.n_parts
+        self._check_refine(exchange)
         dp_mode = self.shard is not None or exchange is not None
         if self.dataset is not None:
             batch = None

@@ -9,6 +9,9 @@ RayMarcher.backward).
     refiner = PoseRefiner(len(poses)).to(device)
     rays_o, rays_d = data.get_rays(directions, refiner(poses[img_idxs], img_idxs))
     loss(render(model, rays_o, rays_d)).backward()      # refiner.dR.grad, refiner.dT.grad
+
+The fused step trains the same offsets inside its graphs (engine.StepConfig(refine_poses=True),
+trainer.HParams(optimize_ext=True); csrc/pose.hip); fused_offsets() / fused_refined_poses() read them.
 """
 import torch
 from torch import nn
@@ -56,3 +59,24 @@ class PoseRefiner(nn.Module):
     def optimizer(self, lr=POSE_LR):
         """The reference's second optimizer (train.py:139): Adam over [dR, dT] at a fixed 1e-6."""
         return torch.optim.Adam([self.dR, self.dT], lr)
+
+
+# ---------------------------------------------------------------------------- the fused step's poses
+def fused_offsets(step):
+    """(dR, dT), each (n_images, 3): the offsets an engine.TrainStep(StepConfig(refine_poses=True))
+    trains, the device tensors themselves (read them after a synchronisation; the step's kernels
+    update them in place)."""
+    if not step.cfg.refine_poses or getattr(step, "dR", None) is None:
+        raise ValueError("the step does not refine poses (StepConfig.refine_poses with an attached dataset)")
+    return step.dR, step.dT
+
+
+def fused_refined_poses(step):
+    """[R(dR) @ R0 | t0 + dT] of every image (n_images,3,4) from the step's current offsets: forward()
+    of a PoseRefiner holding them."""
+    dR, dT = fused_offsets(step)
+    ref = PoseRefiner(dR.shape[0]).to(dR.device)
+    with torch.no_grad():
+        ref.dR.copy_(dR)
+        ref.dT.copy_(dT)
+    return ref.refined_poses(step.dataset.poses)

@@ -54,6 +54,8 @@ class HParams:
     rgb_layers: int = 2
     seed: int = 1337
     steps_per_epoch: int = 1000  # len(train dataset) (datasets/base.py:17-20)
+    optimize_ext: bool = False   # camera-pose refinement (opt.py:47, train.py:91-94, 122-139)
+    pose_lr: float = 1e-6        # train.py:139 hard-codes it
 
 
 def cosine_lr(epoch, hp: HParams):
@@ -74,10 +76,14 @@ class Trainer:
             raise NotImplementedError("the fused step trains with a fixed background (random_bg off)")
         if hp.rgb_layers != 2:
             raise NotImplementedError("the fused field head implements rgb_layers=2")
+        if hp.optimize_ext and world > 1:
+            raise NotImplementedError("optimize_ext (pose refinement) runs on one GPU: the per-image offsets are "
+                                      "not exchanged between ranks")
         self.hp, self.train = hp, train
         cfg = engine.StepConfig(n_rays=hp.batch_size, scale=hp.scale, L=hp.L, F=hp.F, log2_T=hp.T, N_min=hp.N_min,
                                 N_max=hp.N_max, grid=hp.grid, N_tables=hp.N_tables, rgb_width=hp.rgb_channels,
-                                lr=hp.lr, lambda_distortion=hp.distortion_loss_w)
+                                lr=hp.lr, lambda_distortion=hp.distortion_loss_w, refine_poses=hp.optimize_ext,
+                                pose_lr=hp.pose_lr)
         self.step = engine.TrainStep(cfg, device=device, seed=hp.seed)
         if world > 1:
             self.step.shard_optimizer(rank, world)
@@ -191,11 +197,23 @@ class Trainer:
             vals.append(psnr(res["rgb"].float(), img.to(dev)))
         return sum(vals) / len(vals), vals
 
+    def refined_poses(self):
+        """Every training image's refined pose (n_img,3,4) from the current dR / dT (train.py:295); the
+        dataset's own poses without optimize_ext."""
+        if not self.hp.optimize_ext:
+            return self.train.poses.clone()
+        from .pose import fused_refined_poses
+        return fused_refined_poses(self.step)
+
     def state_dict(self):
-        """The reference's keys (NeRFSystem.state_dict -> 'model.*'; utils.py:4-39)."""
+        """The reference's keys (NeRFSystem.state_dict -> 'model.*'; utils.py:4-39); with optimize_ext
+        also its parameters dR and dT (train.py:122-128).  'poses' stays the dataset's."""
         m = self.to_ngp()
         sd = {"model." + k: v.detach().cpu() for k, v in m.state_dict().items()}
         sd["poses"] = self.train.poses.detach().cpu()
+        if self.hp.optimize_ext:
+            sd["dR"] = self.step.dR.detach().cpu()
+            sd["dT"] = self.step.dT.detach().cpu()
         return sd
 
     def save(self, path):
@@ -231,3 +249,17 @@ class Trainer:
             st.density_grid.copy_(sd["model.density_grid"].to(st.dev))
         if "model.density_bitfield" in sd:
             st.bitfield.copy_(sd["model.density_bitfield"].to(st.dev))
+        if self.hp.optimize_ext:
+            # the offsets when the checkpoint has them, fresh pose moments either way (as the field's),
+            # and both refined-pose buffers recomposed with nothing in flight
+            torch.cuda.synchronize(st.dev)
+            for name, dst in (("dR", st.dR), ("dT", st.dT)):
+                if name in sd:
+                    if tuple(sd[name].shape) != tuple(dst.shape):
+                        raise ValueError(f"checkpoint {name} does not match this dataset's image count")
+                    dst.copy_(sd[name].float().to(st.dev))
+            st.pose_m.zero_()
+            st.pose_v.zero_()
+            st.pose_step_dev.zero_()
+            st.compose_poses()
+            st._primed = False  # a batch drawn ahead came from the old poses
