@@ -14,7 +14,8 @@
  * Reference interfaces replaced (lly00412/MF-NeRF, paths relative to the repo root):
  *   vren pybind module: models/csrc/binding.cpp:234-250 (C++ signatures binding.cpp:4-231,
  *   models/csrc/include/utils.h:9-126); tiny-cuda-nn HashGrid / SphericalHarmonics /
- *   FullyFusedMLP as configured in models/networks.py:36-79; apex FusedAdam (train.py:136).
+ *   FullyFusedMLP as configured in models/networks.py:36-79; apex FusedAdam (train.py:136);
+ *   torchmetrics PSNR / SSIM of the validation step (train.py:65-67, 198-237).
  */
 #ifndef MFNERF_H
 #define MFNERF_H
@@ -499,6 +500,27 @@ int mfnerf_occupancy_update_dev(float* density_grid, const float* sigmas, const 
                                 const int32_t* n_dev, int cascades, int grid_size, float decay, const float* count_grid,
                                 float density_threshold, float* tmp, int tmp_zero, uint8_t* bitfield,
                                 void* workspace, mfnerf_stream_t stream);
+
+/* ---------------------------------------------------------------- validation metrics */
+
+/* The validation metrics of one rendered view against its ground truth (train.py:65-67, 198-237:
+ * torchmetrics PeakSignalNoiseRatio(data_range=1) and StructuralSimilarityIndexMeasure(data_range=1),
+ * logged as test/psnr and test/ssim).  pred, target (H*W, 3) f32, row-major pixels, rgb interleaved.
+ * out (2) f64, device: out[0] = mse = mean((pred - target)^2) over all 3*H*W values (the reference's
+ * PSNR is 10*log10(1/mse)); out[1] = ssim = the mean over the three channels and the pixels whose
+ * 11x11 window lies inside the image (5 <= y <= H-6, 5 <= x <= W-6) of
+ *     ((2 mp mt + c1)(2 spt + c2)) / ((mp^2 + mt^2 + c1)(sp2 + st2 + c2)),  c1 = 0.01^2, c2 = 0.03^2,
+ * the moments taken under the separable Gaussian window g[k] ~ exp(-(k-5)^2 / (2*1.5^2)), k = 0..10,
+ * normalised to sum 1 -- torchmetrics' value: it pads by reflection and crops the padded border
+ * from the map before the mean.  Inputs fp32; every product, filter sum, the expression and both
+ * reductions fp64 (E[x^2] - mu^2 cancels in fp32 on flat bright windows); pred == target gives exactly
+ * {0, 1}.  Fixed summation order, no atomics: the same bits on every run.  workspace:
+ * mfnerf_image_metrics_workspace(H, W) bytes, any contents.  H < 11 or W < 11: MFN_ERR_INVALID,
+ * nothing is launched and out is untouched (the workspace query returns 0).  No allocation and no
+ * host read: legal inside stream capture. */
+int64_t mfnerf_image_metrics_workspace(int64_t H, int64_t W);
+int mfnerf_image_metrics(const float* pred, const float* target, int64_t H, int64_t W, double* out,
+                         void* workspace, mfnerf_stream_t stream);
 
 /* ---------------------------------------------------------------- training batch */
 

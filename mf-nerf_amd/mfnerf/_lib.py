@@ -65,6 +65,8 @@ SIGNATURES = {
     "mfnerf_composite_test_fw": (_I, [_P, _P, _P, _P, _P, _I64, _I, _F, _P, _P, _P, _P, _P]),
     "mfnerf_render_test_fused": (_I, [_P, _P, _I64, _P, _P, _P, _I, _F, _F, _I, _I, _I, _F, _F, _F,
                                       ctypes.POINTER(GridDesc), _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "mfnerf_image_metrics_workspace": (_I64, [_I64, _I64]),
+    "mfnerf_image_metrics": (_I, [_P, _P, _I64, _I64, _P, _P, _P]),
     "mfnerf_distortion_loss_fw": (_I, [_P, _P, _P, _P, _I64, _I64, _P, _P, _P, _P]),
     "mfnerf_distortion_loss_bw": (_I, [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P]),
     "mfnerf_nerf_loss": (_I, [_P, _P, _P, _I64, _I64, _F, _F, _F, _F, _P, _P, _P, _P]),

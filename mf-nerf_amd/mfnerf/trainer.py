@@ -15,8 +15,9 @@ the step.
   unpinned: the parity fixtures come from an fp32 reference and assert zero skips).  All of it on the
   device (mfnerf_field_bw's non-finite flag and device scale, the optimizer pass's last workgroup
   running GradScaler.update(); mfnerf_amp_state) -- no host synchronisation;
-* metrics -- train loss / PSNR / rm_s (train.py:178-189), test PSNR with the test-time renderer
-  (train.py:197-206), both read back only every `log_every` steps;
+* metrics -- train loss / PSNR / rm_s (train.py:178-189), read back only every `log_every` steps;
+  test PSNR with the test-time renderer (evaluate, train.py:197-206) and test PSNR + SSIM
+  (validate, train.py:198-237: mfnerf.metrics, fp64 on the device, one read-back per test set);
 * checkpoints -- the reference's state-dict keys (model.xyz_encoder.params, model.rgb_net.params,
   model.density_bitfield, ...; utils.py:4-39), loaded with torch.load(weights_only=True).
 The data step is GPU-resident (mfnerf.data.DeviceDataset): no DataLoader, no host copies.
@@ -196,6 +197,39 @@ class Trainer:
             res = render_fused(model, o, d, **kw) if fused else render(model, o, d, **kw)
             vals.append(psnr(res["rgb"].float(), img.to(dev)))
         return sum(vals) / len(vals), vals
+
+    @torch.no_grad()
+    def validate(self, images, poses, directions, img_wh=None, fused=False):
+        """validation_step / validation_epoch_end (train.py:198-237): test PSNR and SSIM of every
+        (images[i], poses[i]) view, rendered exactly as evaluate() renders it, and their means over
+        the views.  Each view's [mse, ssim] (metrics.image_metrics, fp64) goes into its row of one
+        device tensor that is read back once after the last view: no host synchronisation between
+        the renders.  img_wh = (W, H) defaults to the training set's.
+        Returns {"psnr", "ssim", "psnr_per_view", "ssim_per_view"}."""
+        from .data import get_rays
+        from .metrics import image_metrics, psnr_from_mse, workspace_bytes
+        from .rendering import render, render_fused
+        img_wh = self.train.img_wh if img_wh is None else img_wh
+        if img_wh is None:
+            raise ValueError("validate needs img_wh (the training set carries none)")
+        model = self.to_ngp()
+        dev = self.step.dev
+        dirs = directions.to(dev)
+        table = torch.empty(len(images), 2, dtype=torch.float64, device=dev)
+        ws = torch.empty(workspace_bytes(img_wh[1], img_wh[0]), dtype=torch.uint8, device=dev)
+        for i, (img, pose) in enumerate(zip(images, poses)):
+            o, d = get_rays(dirs, pose.to(dev))
+            kw = {} if fused else {"test_time": True}
+            if self.hp.scale > 0.5:
+                kw["exp_step_factor"] = 1 / 256
+            res = render_fused(model, o, d, **kw) if fused else render(model, o, d, **kw)
+            image_metrics(res["rgb"].float().contiguous(), img.to(dev, torch.float32).contiguous(), img_wh,
+                          out=table[i], workspace=ws)
+        table[:, 0] = psnr_from_mse(table[:, 0])
+        host = table.cpu()  # the one read
+        psnrs, ssims = host[:, 0].tolist(), host[:, 1].tolist()
+        return {"psnr": sum(psnrs) / len(psnrs), "ssim": sum(ssims) / len(ssims),
+                "psnr_per_view": psnrs, "ssim_per_view": ssims}
 
     def refined_poses(self):
         """Every training image's refined pose (n_img,3,4) from the current dR / dT (train.py:295); the

@@ -5,7 +5,7 @@ views with the test-time renderer (train.py:197-206).  The Lego images are not i
 scene is the bench's 12-ball scene with a world-space surface texture (detail for the fine levels).
 
 Prints one JSON line: training wall time (occupancy refreshes, lr steps and logging included),
-whole-run rays/s, per-1000-step train PSNR / rm_s, and the test PSNR.
+whole-run rays/s, per-1000-step train PSNR / rm_s, and the test PSNR and SSIM.
 
     python tools/train_30k.py [--epochs 30] [--tex 40] [--views 100] [--test-views 8]
 """
@@ -71,6 +71,7 @@ def main():
     t1 = time.perf_counter()
     test_psnr, per_view = tr.evaluate(t_imgs, t_poses, dirs)
     eval_s = time.perf_counter() - t1
+    val = tr.validate(t_imgs, t_poses, dirs)  # test/ssim beside test/psnr (train.py:198-237)
     white = sum(float(-10 * torch.log10(((1 - im) ** 2).mean())) for im in t_imgs) / len(t_imgs)
     print(json.dumps({
         "protocol": f"{'benchmark_synthetic_nerf_mf.sh' if args.mf else 'train.py defaults'}: {steps} steps x "
@@ -81,6 +82,7 @@ def main():
                  f"{args.test_views} held-out views at {W}x{W}, Lego intrinsics",
         "train_wall_s": round(wall, 2), "rays_per_s_whole_run": round(steps * hp.batch_size / wall, 1),
         "test_psnr": round(test_psnr, 3), "test_psnr_per_view": [round(v, 3) for v in per_view],
+        "test_ssim": round(val["ssim"], 4), "test_ssim_per_view": [round(v, 4) for v in val["ssim_per_view"]],
         "white_image_psnr": round(white, 3), "eval_s": round(eval_s, 2), "skipped_steps": hist[-1]["skipped"],
         # records the partitioned scatter's slots could not hold (added by atomics), per logged
         # interval of steps_per_epoch steps and in total
