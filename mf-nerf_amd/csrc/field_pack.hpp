@@ -1,5 +1,5 @@
 // field_pack.hpp -- the MFMA weight-fragment layout of field.hip (and the repack that builds it),
-// shared with grid.hip, whose optimizer tail repacks the MLP weights in its own launch.
+// shared with grid_adam_fixed.hpp, whose optimizer tail repacks the MLP weights in its own launch.
 #pragma once
 
 #include <hip/hip_runtime.h>

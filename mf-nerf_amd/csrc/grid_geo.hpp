@@ -1,5 +1,5 @@
 // grid_geo.hpp -- one level's cell geometry, corner index and corner weight of the multiresolution
-// grid encoding (tcnn HashGrid semantics plus the MixedFeature shared tables), shared by grid.hip
+// grid encoding (tcnn HashGrid semantics plus the MixedFeature shared tables), shared by the grid_*.hip
 // and render.hip.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -13,7 +13,7 @@
 //
 // Lane mapping: as grid_fw_kernel, 4 lanes per sample, each lane 4 consecutive levels -- its 8
 // incoming gradients are two 16-B loads, and all 32 of its corner gathers are issued before any is
-// used (the encode is bound by per-lane gather addresses, grid.hip).  The four lanes' partial
+// used (the encode is bound by per-lane gather addresses, grid_fw.hip).  The four lanes' partial
 // 3-vectors are added by two xor-shuffles (a fixed order).
 #include "common.hpp"
 #include "grid_geo.hpp"
@@ -22,7 +22,7 @@
 using namespace mfn;
 using namespace mfn_grid;
 
-int mfn_check_grid_desc(const mfnerf_grid_desc* d, const char* what);  // grid.hip
+int mfn_check_grid_desc(const mfnerf_grid_desc* d, const char* what);  // grid_fw.hip
 
 namespace {
 
