@@ -10,8 +10,8 @@
 //   LDS round trip (cdna_hip_programming.md section 3, "An accumulator tile as the next MFMA's
 //   operand").  The weights are the A operands, pre-permuted once per optimizer step by
 //   mfnerf_field_pack_weights into 1-KiB lane-linear fragments (ds_read_b128, conflict-free).
-//   Backward: see the comments above field_bw_coop_kernel (W = 64) and field_bw_coop128_kernel.
-#include <cstdlib>
+//   Backward: see the comment above field_bw_coop_kernel.
+#include <type_traits>
 
 #include "common.hpp"
 #include "mfma_pack.hpp"
@@ -28,7 +28,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 namespace {
 
 // Backward: 4 waves per workgroup, each the forward + data-gradient chain of its own 32-sample tile,
-// the weight-gradient tiles split over the waves (field_bw_coop_kernel, field_bw_coop128_kernel).
+// the weight-gradient tiles split over the waves (field_bw_coop_kernel).
 // Rounds 1-4 held every tile in each wave (one wave per SIMD; at W = 128 a second pass recomputed the
 // forward for dWr2's 16 tiles: 0.46 vs 0.23 ms on the mf128 step, profiles/r05_v8_*).
 // Measured and not kept (rounds 1-2): every tile in an LDS image with two waves per SIMD (ds_add_f32
@@ -143,12 +143,6 @@ __device__ __forceinline__ void load_tile_in(const _Float16* __restrict__ feat, 
 }
 
 template <int W, bool DENSITY_ONLY>
-__device__ __forceinline__ void forward_tile(const _Float16* lds, int lane, const TileIn& I, bool valid,
-                                             FwdTile<W>& T) {
-    forward_tiles<W, DENSITY_ONLY, 1>(lds, lane, &I, &valid, &T);
-}
-
-template <int W, bool DENSITY_ONLY>
 __global__ __launch_bounds__(FIELD_BLOCK) void field_fw_kernel(const _Float16* __restrict__ feat,
                                                                 int64_t plane_stride,
                                                                 const float* __restrict__ dirs, int64_t n,
@@ -210,11 +204,11 @@ __global__ __launch_bounds__(FIELD_BLOCK) void field_fw_kernel(const _Float16* _
 // written to a per-wave LDS tile image and read back with the transposing ds_read_b64_tr_b16
 // (t_put / s_get above; exact, no wave-level synchronisation).
 //   dW[out][in] (32x32 tile) += S(dY)[out-tile] x S(X)[in-tile], K = the tile's 32 samples (2 MFMAs)
-// The dW tiles accumulate across all sample tiles a wave processes (persistent grid) in registers
-// or in the workgroup's LDS image (BwCfg), then one slab row per workgroup, summed in a fixed order
-// by slab_reduce_kernel.
+// The dW tiles accumulate across all sample tiles a workgroup processes (persistent grid) in
+// registers, split over its waves (field_bw_coop_kernel), then one slab row per workgroup, summed
+// in a fixed order by slab_reduce_kernel.
 
-template <int W, int NW>
+template <int W>
 __device__ __forceinline__ void load_frags_bw(_Float16* lds, const _Float16* __restrict__ packed) {
     using G = Geo<W>;
     const uint4* src = reinterpret_cast<const uint4*>(packed);
@@ -242,13 +236,10 @@ __device__ __forceinline__ SOp s_get(const _Float16* slot, int lane) {
     return o;
 }
 
-__device__ __forceinline__ void dw_acc(f32x16& acc, const SOp& dy, const SOp& x) {
-    acc = mfma(dy.k[0], x.k[0], acc);
-    acc = mfma(dy.k[1], x.k[1], acc);
-}
-// The same product into a PERSISTENT accumulator pinned to AGPRs: with MFMA results in VGPRs
-// (-amdgpu-mfma-vgpr-form, which the data-gradient chain needs) the compiler otherwise moves each
-// of the 12 accumulator tiles AGPR <-> VGPR around every update (~500 v_accvgpr moves per tile).
+// one dW tile += dY x X (K = the tile's 32 samples: 2 MFMAs) into a PERSISTENT accumulator pinned to
+// AGPRs: with MFMA results in VGPRs (-amdgpu-mfma-vgpr-form, which the data-gradient chain needs) the
+// compiler otherwise moves each accumulator tile AGPR <-> VGPR around every update (~500 v_accvgpr
+// moves per sample tile with 12 of them).
 // The leading s_nop covers the VALU-write -> MFMA-read hazard on the packed operands (the compiler's
 // hazard recognizer does not look into inline asm); back-to-back accumulation into the same
 // registers needs none.  Readers of the accumulators wait with xdl_drain().
@@ -261,9 +252,6 @@ __device__ __forceinline__ void dw_acc_agpr(f32x16& acc, const SOp& dy, const SO
 }
 __device__ __forceinline__ void xdl_drain() { asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7\n\ts_nop 7" ::: "memory"); }
 
-// add one 32x32 dW tile (row = out 32*ot + (i&3)+8(i>>2)+4h, col = in 32*it + lane&31) into a
-// row-major fp32 LDS image of a (rows x cols) matrix; rows/cols are compile-time at every call, so
-// the register rows that can never be in range are dropped statically
 // A workgroup's slab row holds non-finite values: raise the step's flag now.  Every row finite
 // bounds every slab sum: |row value| <= (samples of one workgroup) x 65504^2 (fp16 operands,
 // f32 accumulation) ~ 1e13, 512 rows ~ 5e15, far below the f32 range -- so with the rows checked
@@ -273,21 +261,18 @@ __device__ __forceinline__ void slab_row_flag(int32_t* nonfinite, bool bad) {
     if (nonfinite && __any(bad) && (threadIdx.x & 63) == 0) atomicOr(nonfinite, 1);
 }
 
-__device__ __forceinline__ void dw_add32(float* img, const f32x16& a, int ot, int it, int rows, int cols, int lane,
-                                         bool store = false) {
+// store one 32x32 dW tile (row = out 32*ot + (i&3)+8(i>>2)+4h, col = in 32*it + lane&31) into a
+// row-major fp32 LDS image of a (rows x cols) matrix (every entry belongs to one tile, so the waves'
+// stores are disjoint); rows/cols are compile-time at every call, so the register rows that can
+// never be in range are dropped statically
+__device__ __forceinline__ void dw_store32(float* img, const f32x16& a, int ot, int it, int rows, int cols, int lane) {
     const int col = 32 * it + (lane & 31), h = lane >> 5;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
         const int row = 32 * ot + (i & 3) + 8 * (i >> 2) + 4 * h;
-        if (row < rows && col < cols) {
-            if (store) img[row * cols + col] = a[i];  // the first wave of a fixed-order sum
-            else atomicAdd(img + row * cols + col, a[i]);
-        }
+        if (row < rows && col < cols) img[row * cols + col] = a[i];
     }
 }
-
-// one dW tile += dY x X into its register accumulator
-__device__ __forceinline__ void acc_tile(f32x16& reg, const SOp& dy, const SOp& x) { dw_acc_agpr(reg, dy, x); }
 
 // dL/dd of one sample from dL/dSH (mfnerf_field_bw_inputs).  dsh is the 32-row accumulator of
 // d[SH;h] = Wr1^T dR1, still scaled by the loss scale: register i < 8 of lane half h is SH row
@@ -332,45 +317,70 @@ __device__ __forceinline__ void sh4_bw_dir(const f32x16& dsh, int h, float invS,
     out[2] = (gz - z * t) / nrm;
 }
 
-// ---------------------------------------------------------------- cooperative backward (W = 64)
-// The round 1-3 per-wave backward held all 12 weight-gradient tiles in each wave (192 accumulator registers + ~170
-// for the chain): one wave per SIMD, nothing hides the chain's dependencies (PMC: waiting 56 % of
-// its cycles).  Here the 12 tiles are split over the workgroup's 4 waves -- 3 each, 48 accumulator
-// registers -- so a wave fits 256 registers and TWO workgroups share a CU (76 KB of LDS each: the
-// 44 fragments + 4 transpose images per wave), two waves per SIMD.  Each wave still runs the
-// forward and the data-gradient chain of its own 32-sample tile; the weight-gradient operands (the
-// transposed T chunks, t_put) are written stage by stage into the wave's 4 images, the workgroup
-// synchronises, and each wave accumulates ITS tiles of that stage over all four waves' sample tiles
-// (waves 0..3 in order: a fixed summation order, deterministic).  Tiles per wave:
+// ---------------------------------------------------------------- cooperative backward
+// field_bw_coop_kernel<W, PLANAR, DDIRS>, both widths.  Each of the workgroup's 4 waves runs the
+// forward and the data-gradient chain of its own 32-sample tile; the weight-gradient tiles are split
+// over the waves.  The weight-gradient operands (the transposed T chunks, t_put) are written stage by
+// stage into the wave's transpose images, the workgroup synchronises, and each wave accumulates ITS
+// tiles of that stage over all four waves' sample tiles (waves 0..3 in order: a fixed summation
+// order, deterministic).  The chain's next MFMAs are issued between a stage's writes and its products.
+//
+// W = 64 (round 4): 12 tiles, 3 per wave -- 48 accumulator registers, so a wave fits 256 registers
+// and TWO workgroups share a CU, two waves per SIMD.  LDS: the 44 fragments + 4 images per wave,
+// 76 KB per workgroup.  Tiles per wave:
 //   wave 0: dWr3[0], dWr2[0][0], dW2[0]      wave 2: dWr1[0], dWr2[1][0], dW1[0]
 //   wave 1: dWr3[1], dWr2[0][1], dW2[1]      wave 3: dWr1[1], dWr2[1][1], dW1[1]
 // Stages (images per wave): S1 dO, R2 x2 | S2 dR2 x2, R1 x2 | S3 dR1 x2, [SH;h] | S4 dh, Y1 x2 |
-// S5 dY1 x2, X; the chain's next MFMAs are issued between a stage's writes and its products.
-constexpr int COOP_SLOTS = 4;      // transpose images per wave live at once (stage 2)
-constexpr int COOP_BLOCKS = 512;   // two workgroups per CU (persistent)
-constexpr size_t COOP_LDS = (size_t)Geo<64>::N * FRAG_HALFS * 2 + (size_t)4 * COOP_SLOTS * TILE_BYTES;
-static_assert(COOP_LDS <= 80 * 1024, "two cooperative workgroups per CU");
+// S5 dY1 x2, X.
+// Before (rounds 1-3) every wave held all 12 tiles (192 accumulator registers + ~170 for the
+// chain): one wave per SIMD, nothing hid the chain's dependencies (PMC: waiting 56 % of its cycles).
+//
+// W = 128 (round 5; configs 3/4, MF-NeRF's benchmark field): 28 tiles, 7 per wave -- 112
+// accumulator registers pinned to AGPRs, one wave per SIMD.  LDS: all 106 fragments (106 KB) beside
+// 6 images per wave (48 KB), one workgroup per CU.  Tiles per wave w:
+//   dWr3[w] (16 x 32 block w of the 16 x 128), dWr2[w][0..3] (row block w), dWr1[w],
+//   and dW2[w] (waves 0, 1) or dW1[w - 2] (waves 2, 3).
+// Stages (images per wave): S1 dO, R2 x4 | S2a dR2 x4, R1[0..1] | S2b R1[2..3] over R1[0..1] |
+// S3 dR1 x4, [SH;h] | S4 dh, Y1 x2 | S5 dY1 x2, X.
+// Before (rounds 1-4) every wave held all tiles but dWr2's 16 (448 accumulator registers do not
+// fit), and a second pass recomputed the forward and dR2 for them: 0.46 ms of the 1.67 ms mf128
+// step (profiles/r04_final_bench_mf128.json).
+template <int W>
+struct CoopGeo {
+    static constexpr int SLOTS = W == 64 ? 4 : 6;          // transpose images per wave live at once
+    static constexpr int BLOCKS = W == 64 ? 512 : 256;     // persistent workgroups = slab rows (two | one per CU)
+    static constexpr int WAVES_PER_SIMD = W == 64 ? 2 : 1;
+    static constexpr size_t LDS = (size_t)Geo<W>::N * FRAG_HALFS * 2 + (size_t)4 * SLOTS * TILE_BYTES;
+    static_assert(W != 64 || LDS <= 80 * 1024, "two cooperative workgroups per CU");
+    static_assert(W != 128 || LDS <= 160 * 1024, "one cooperative W = 128 workgroup per CU");
+};
 
-template <bool PLANAR, bool DDIRS = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void field_bw_coop_kernel(
+template <int W, bool PLANAR, bool DDIRS>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CoopGeo<W>::WAVES_PER_SIMD))) void field_bw_coop_kernel(
     const _Float16* __restrict__ feat, int64_t plane_stride, const float* __restrict__ dirs, int64_t n,
     const int32_t* __restrict__ n_dev, const _Float16* __restrict__ packed, const float* __restrict__ dL_dsigma,
     const float* __restrict__ dL_drgb, float grad_scale, const float* __restrict__ scale_dev,
     float* __restrict__ dL_dfeat, float* __restrict__ slab, int32_t* __restrict__ nonfinite, float* __restrict__ level_l1,
     float* __restrict__ dL_ddirs) {
-    constexpr int W = 64;
     using G = Geo<W>;
-    constexpr int MT = G::MT;
+    constexpr int MT = G::MT, SLOTS = CoopGeo<W>::SLOTS;
     constexpr int oR1 = N_XYZ_PARAMS, oR2 = oR1 + W * 32, oR3 = oR2 + W * W;
     constexpr size_t IMG_OFF = (size_t)G::N * FRAG_HALFS * 2;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     _Float16* lds_base = reinterpret_cast<_Float16*>(smem);
-    load_frags_bw<W, 4>(lds_base, packed);
+    load_frags_bw<W>(lds_base, packed);
     const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (uniform)
     const int r = lane & 31, h = lane >> 5;
     const float S = scale_dev ? *scale_dev : grad_scale, invS = 1.0f / S;
     const f32x16 z = {};
-    f32x16 acc0 = z, acc1 = z, acc2 = z;  // this wave's three tiles (table above)
+    // this wave's weight-gradient tiles (tables above): plain variables, the other width's unused
+    // and free (as members of a per-width struct they compile to other code)
+    f32x16 a_r13 = z, a_r2 = z;          // W = 64: dWr3 (waves 0, 1) | dWr1 (waves 2, 3); dWr2[w >> 1][w & 1]
+    f32x16 a_r3 = z, a_r1 = z;           // W = 128: dWr3[w], dWr1[w]
+    f32x16 a_x = z;                      // both: dW2[w] (waves 0, 1) | dW1[w - 2] (waves 2, 3)
+    f32x16 a_r2w[MT];                    // W = 128: dWr2[w][0..3]
+#pragma unroll
+    for (int i = 0; i < MT; ++i) a_r2w[i] = z;
     const int64_t nn = n_dev ? min<int64_t>(n, (int64_t)*n_dev) : n;
     const int64_t tiles = div_up<int64_t>(nn, 32);
     const int64_t groups = div_up<int64_t>(tiles, 4);  // group g = tiles 4g .. 4g+3, one per wave
@@ -415,7 +425,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void f
         asm volatile("" : "+s"(opaque));
         const _Float16* lds = lds_base + opaque;
         _Float16* area = lds_base + opaque + IMG_OFF / 2;
-        auto slot = [&](int u, int k) { return area + (u * COOP_SLOTS + k) * TILE_HALFS; };
+        auto slot = [&](int u, int k) { return area + (u * SLOTS + k) * TILE_HALFS; };
         auto put2 = [&](_Float16* sl, const half8* v) {  // a 32-channel tile as two perm chunks
             t_put(sl, lane, v[0], 0, true);
             t_put(sl, lane, v[1], 4, true);
@@ -444,14 +454,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void f
             dr2p[mt][0] = relu_mask8(pack8<0, false>(a), T.r2[mt][0]);
             dr2p[mt][1] = relu_mask8(pack8<8, false>(a), T.r2[mt][1]);
         }
-        // ---- S1: dO, R2 -> dWr3 (waves 0, 1)
+        // ---- S1: dO, R2 -> dWr3 (W = 64: waves 0, 1; W = 128: dWr3[w])
+        // (S1-S3's puts stay per width: W = 64's two as a loop over MT compile to other code)
         t_put(slot(wid, 0), lane, dOb, 0, true);  // (channels 16..31 stale: rows 16..31 of dWr3, dropped)
-        put2(slot(wid, 1), T.r2[0]);
-        put2(slot(wid, 2), T.r2[1]);
-        __syncthreads();
-        if (wid < 2) {
+        if constexpr (W == 64) {
+            put2(slot(wid, 1), T.r2[0]);
+            put2(slot(wid, 2), T.r2[1]);
+            __syncthreads();
+            if (wid < 2) {
 #pragma unroll
-            for (int u = 0; u < 4; ++u) acc_tile(acc0, s_get(slot(u, 0), lane), s_get(slot(u, 1 + wid), lane));
+                for (int u = 0; u < 4; ++u) dw_acc_agpr(a_r13, s_get(slot(u, 0), lane), s_get(slot(u, 1 + wid), lane));
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < MT; ++i) put2(slot(wid, 1 + i), T.r2[i]);
+            __syncthreads();
+#pragma unroll
+            for (int u = 0; u < 4; ++u) dw_acc_agpr(a_r3, s_get(slot(u, 0), lane), s_get(slot(u, 1 + wid), lane));
         }
         //    dR1 = Wr2^T dR2, masked by R1 > 0
         half8 dr1p[MT][2];
@@ -466,11 +485,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void f
             dr1p[mt][1] = relu_mask8(pack8<8, false>(a), T.r1[mt][1]);
         }
         __syncthreads();
-        // ---- S2: dR2, R1 -> dWr2 (one tile per wave)
-        put2(slot(wid, 0), dr2p[0]);
-        put2(slot(wid, 1), dr2p[1]);
-        put2(slot(wid, 2), T.r1[0]);
-        put2(slot(wid, 3), T.r1[1]);
+        // ---- S2 (W = 128: S2a): dR2, R1[0..1] -> dWr2 (W = 64: one tile per wave; W = 128: dWr2[w][0..1])
+        if constexpr (W == 64) {
+            put2(slot(wid, 0), dr2p[0]);
+            put2(slot(wid, 1), dr2p[1]);
+            put2(slot(wid, 2), T.r1[0]);
+            put2(slot(wid, 3), T.r1[1]);
+        } else {
+#pragma unroll
+            for (int o = 0; o < MT; ++o) put2(slot(wid, o), dr2p[o]);
+            put2(slot(wid, 4), T.r1[0]);
+            put2(slot(wid, 5), T.r1[1]);
+        }
         //    d[SH;h] = Wr1^T dR1 (rows 16..31 = dh) + TruncExp backward into h[0]
         half8 dhb;
         {
@@ -497,10 +523,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void f
             }
         }
         __syncthreads();
-        {
+        if constexpr (W == 64) {
             const int o = wid >> 1, i = wid & 1;
 #pragma unroll
-            for (int u = 0; u < 4; ++u) acc_tile(acc1, s_get(slot(u, o), lane), s_get(slot(u, 2 + i), lane));
+            for (int u = 0; u < 4; ++u) dw_acc_agpr(a_r2, s_get(slot(u, o), lane), s_get(slot(u, 2 + i), lane));
+        } else {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const SOp d = s_get(slot(u, wid), lane);
+                dw_acc_agpr(a_r2w[0], d, s_get(slot(u, 4), lane));
+                dw_acc_agpr(a_r2w[1], d, s_get(slot(u, 5), lane));
+            }
         }
         //    dY1 = W2^T dh, masked by Y1 > 0; dX = W1^T dY1
         half8 dy1p[2][2];
@@ -518,18 +551,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void f
                 for (int k = 0; k < 2; ++k) dx = mfma(lds_frag(lds, G::B1 + t * 2 + k, lane), dy1p[t][k], dx);
         }
         __syncthreads();
-        // ---- S3: dR1, [SH;h] -> dWr1 (waves 2, 3)
-        put2(slot(wid, 0), dr1p[0]);
-        put2(slot(wid, 1), dr1p[1]);
-        t_put(slot(wid, 2), lane, T.sh, 0, false);
-        t_put(slot(wid, 2), lane, T.hb, 4, true);
-        __syncthreads();
-        if (wid >= 2) {
+        // dX -> global fp32 (features (i&3)+8(i>>2)+4h), this wave's own tile.  The store sits where
+        // each width's schedule has it, so its body is here twice: called as a lambda or a function
+        // from the two places it compiles to other code
+        if constexpr (W == 64) {
+            // ---- S3: dR1, [SH;h] -> dWr1 (waves 2, 3)
+            put2(slot(wid, 0), dr1p[0]);
+            put2(slot(wid, 1), dr1p[1]);
+            t_put(slot(wid, 2), lane, T.sh, 0, false);
+            t_put(slot(wid, 2), lane, T.hb, 4, true);
+            __syncthreads();
+            if (wid >= 2) {
 #pragma unroll
-            for (int u = 0; u < 4; ++u) acc_tile(acc0, s_get(slot(u, wid - 2), lane), s_get(slot(u, 2), lane));
-        }
-        // dX = W1^T dY1 -> global fp32 (features (i&3)+8(i>>2)+4h), this wave's own tile
-        {
+                for (int u = 0; u < 4; ++u) dw_acc_agpr(a_r13, s_get(slot(u, wid - 2), lane), s_get(slot(u, 2), lane));
+            }
             const int64_t s = tile * 32 + r;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
@@ -539,6 +574,35 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void f
                 l1a[q] += fabsf(o.x) + fabsf(o.y);
                 l1b[q] += fabsf(o.z) + fabsf(o.w);
             }
+        } else {
+            // ---- S2b: R1[2..3] over R1[0..1] -> dWr2[w][2..3] (dR2 still in slots 0..3)
+            put2(slot(wid, 4), T.r1[2]);
+            put2(slot(wid, 5), T.r1[3]);
+            __syncthreads();
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const SOp d = s_get(slot(u, wid), lane);
+                dw_acc_agpr(a_r2w[2], d, s_get(slot(u, 4), lane));
+                dw_acc_agpr(a_r2w[3], d, s_get(slot(u, 5), lane));
+            }
+            const int64_t s = tile * 32 + r;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const float4 o = make_float4(dx[4 * q] * invS, dx[4 * q + 1] * invS, dx[4 * q + 2] * invS, dx[4 * q + 3] * invS);
+                bad |= !(isfinite(o.x) && isfinite(o.y) && isfinite(o.z) && isfinite(o.w));
+                if (s < nn) reinterpret_cast<float4*>(dL_dfeat + s * 32)[2 * q + h] = o;
+                l1a[q] += fabsf(o.x) + fabsf(o.y);
+                l1b[q] += fabsf(o.z) + fabsf(o.w);
+            }
+            __syncthreads();
+            // ---- S3: dR1, [SH;h] -> dWr1[w]
+#pragma unroll
+            for (int o = 0; o < MT; ++o) put2(slot(wid, o), dr1p[o]);
+            t_put(slot(wid, 4), lane, T.sh, 0, false);
+            t_put(slot(wid, 4), lane, T.hb, 4, true);
+            __syncthreads();
+#pragma unroll
+            for (int u = 0; u < 4; ++u) dw_acc_agpr(a_r1, s_get(slot(u, wid), lane), s_get(slot(u, 4), lane));
         }
         __syncthreads();
         // ---- S4: dh, Y1 -> dW2 (waves 0, 1)
@@ -548,7 +612,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void f
         __syncthreads();
         if (wid < 2) {
 #pragma unroll
-            for (int u = 0; u < 4; ++u) acc_tile(acc2, s_get(slot(u, 0), lane), s_get(slot(u, 1 + wid), lane));
+            for (int u = 0; u < 4; ++u) dw_acc_agpr(a_x, s_get(slot(u, 0), lane), s_get(slot(u, 1 + wid), lane));
         }
         __syncthreads();
         // ---- S5: dY1, X -> dW1 (waves 2, 3)
@@ -559,7 +623,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void f
         __syncthreads();
         if (wid >= 2) {
 #pragma unroll
-            for (int u = 0; u < 4; ++u) acc_tile(acc2, s_get(slot(u, wid - 2), lane), s_get(slot(u, 2), lane));
+            for (int u = 0; u < 4; ++u) dw_acc_agpr(a_x, s_get(slot(u, wid - 2), lane), s_get(slot(u, 2), lane));
         }
         __syncthreads();  // the images are rewritten by the next group's S1
     }
@@ -585,303 +649,32 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void f
                 if (r == 0) { atomicAdd(l1_part + 4 * q + 2 * h, a); atomicAdd(l1_part + 4 * q + 2 * h + 1, b); }
             }
         }
-        if (wid == 0) {
-            dw_add32(img + oR3, acc0, 0, 0, 16, W, lane, true);
-            dw_add32(img + oR2, acc1, 0, 0, W, W, lane, true);
-            dw_add32(img + 64 * 32, acc2, 0, 0, 16, 64, lane, true);
-        } else if (wid == 1) {
-            dw_add32(img + oR3, acc0, 0, 1, 16, W, lane, true);
-            dw_add32(img + oR2, acc1, 0, 1, W, W, lane, true);
-            dw_add32(img + 64 * 32, acc2, 0, 1, 16, 64, lane, true);
-        } else if (wid == 2) {
-            dw_add32(img + oR1, acc0, 0, 0, W, 32, lane, true);
-            dw_add32(img + oR2, acc1, 1, 0, W, W, lane, true);
-            dw_add32(img, acc2, 0, 0, 64, 32, lane, true);
+        if constexpr (W == 64) {
+            if (wid == 0) {
+                dw_store32(img + oR3, a_r13, 0, 0, 16, W, lane);
+                dw_store32(img + oR2, a_r2, 0, 0, W, W, lane);
+                dw_store32(img + 64 * 32, a_x, 0, 0, 16, 64, lane);
+            } else if (wid == 1) {
+                dw_store32(img + oR3, a_r13, 0, 1, 16, W, lane);
+                dw_store32(img + oR2, a_r2, 0, 1, W, W, lane);
+                dw_store32(img + 64 * 32, a_x, 0, 1, 16, 64, lane);
+            } else if (wid == 2) {
+                dw_store32(img + oR1, a_r13, 0, 0, W, 32, lane);
+                dw_store32(img + oR2, a_r2, 1, 0, W, W, lane);
+                dw_store32(img, a_x, 0, 0, 64, 32, lane);
+            } else {
+                dw_store32(img + oR1, a_r13, 1, 0, W, 32, lane);
+                dw_store32(img + oR2, a_r2, 1, 1, W, W, lane);
+                dw_store32(img, a_x, 1, 0, 64, 32, lane);
+            }
         } else {
-            dw_add32(img + oR1, acc0, 1, 0, W, 32, lane, true);
-            dw_add32(img + oR2, acc1, 1, 1, W, W, lane, true);
-            dw_add32(img, acc2, 1, 0, 64, 32, lane, true);
+            dw_store32(img + oR3, a_r3, 0, wid, 16, W, lane);
+            dw_store32(img + oR1, a_r1, wid, 0, W, 32, lane);
+#pragma unroll
+            for (int i = 0; i < MT; ++i) dw_store32(img + oR2, a_r2w[i], wid, i, W, W, lane);
+            if (wid < 2) dw_store32(img + 64 * 32, a_x, 0, wid, 16, 64, lane);
+            else dw_store32(img, a_x, wid - 2, 0, 64, 32, lane);
         }
-        __syncthreads();
-        bool rbad = false;  // a non-finite weight-gradient partial (see slab_row_flag)
-        for (int i = threadIdx.x; i < G::N_DW; i += blockDim.x) {
-            const float val = img[i] * invS;
-            row[i] = val;
-            rbad |= !isfinite(val);
-        }
-        slab_row_flag(nonfinite, rbad);
-        if (level_l1 && threadIdx.x < 16) atomicAdd(level_l1 + threadIdx.x, l1_part[threadIdx.x]);
-    }
-}
-
-// ---------------------------------------------------------------- cooperative backward (W = 128)
-// Round 5: the width-128 field (configs 3/4, MF-NeRF's benchmark field) in ONE pass, the W = 64
-// cooperative scheme scaled up.  The per-wave backward (removed) held all weight-gradient tiles but dWr2's
-// 16 (one wave per SIMD, 448 accumulator registers do not fit), and a second pass recomputed the
-// forward and dR2 for them: 0.46 ms of the 1.67 ms mf128 step (profiles/r04_final_bench_mf128.json).
-// Here the 28 tiles are split over the workgroup's 4 waves -- 7 each, 112 accumulator registers
-// pinned to AGPRs -- every wave runs the forward and the data-gradient chain of its own 32-sample
-// tile, writes the weight-gradient operands (transposed T chunks) stage by stage into its images, and
-// after a barrier accumulates ITS tiles of that stage over all four waves' tiles, waves 0..3 in order
-// (a fixed summation order: deterministic).  Tiles per wave w:
-//   dWr3[w] (16 x 32 block w of the 16 x 128), dWr2[w][0..3] (row block w), dWr1[w],
-//   and dW2[w] (waves 0, 1) or dW1[w - 2] (waves 2, 3).
-// All 106 fragments stay in LDS (106 KB) beside 6 images per wave (48 KB): one workgroup per CU.
-// Stages (images per wave): S1 dO, R2 x4 | S2a dR2 x4, R1[0..1] | S2b R1[2..3] over R1[0..1] |
-// S3 dR1 x4, [SH;h] | S4 dh, Y1 x2 | S5 dY1 x2, X.
-constexpr int COOP128_SLOTS = 6;
-constexpr size_t COOP128_LDS = (size_t)Geo<128>::N * FRAG_HALFS * 2 + (size_t)4 * COOP128_SLOTS * TILE_BYTES;
-static_assert(COOP128_LDS <= 160 * 1024, "one cooperative W = 128 workgroup per CU");
-
-template <bool PLANAR, bool DDIRS = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1))) void field_bw_coop128_kernel(
-    const _Float16* __restrict__ feat, int64_t plane_stride, const float* __restrict__ dirs, int64_t n,
-    const int32_t* __restrict__ n_dev, const _Float16* __restrict__ packed, const float* __restrict__ dL_dsigma,
-    const float* __restrict__ dL_drgb, float grad_scale, const float* __restrict__ scale_dev,
-    float* __restrict__ dL_dfeat, float* __restrict__ slab, int32_t* __restrict__ nonfinite, float* __restrict__ level_l1,
-    float* __restrict__ dL_ddirs) {
-    constexpr int W = 128;
-    using G = Geo<W>;
-    constexpr int MT = G::MT;
-    constexpr int oR1 = N_XYZ_PARAMS, oR2 = oR1 + W * 32, oR3 = oR2 + W * W;
-    constexpr size_t IMG_OFF = (size_t)G::N * FRAG_HALFS * 2;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    _Float16* lds_base = reinterpret_cast<_Float16*>(smem);
-    load_frags_bw<W, 4>(lds_base, packed);
-    const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (uniform)
-    const int r = lane & 31, h = lane >> 5;
-    const float S = scale_dev ? *scale_dev : grad_scale, invS = 1.0f / S;
-    const f32x16 z = {};
-    f32x16 a_r3 = z, a_r1 = z, a_x = z, a_r2[MT];  // this wave's seven tiles (table above)
-#pragma unroll
-    for (int i = 0; i < MT; ++i) a_r2[i] = z;
-    const int64_t nn = n_dev ? min<int64_t>(n, (int64_t)*n_dev) : n;
-    const int64_t tiles = div_up<int64_t>(nn, 32);
-    const int64_t groups = div_up<int64_t>(tiles, 4);  // group g = tiles 4g .. 4g+3, one per wave
-    struct BwIn { TileIn I; float gs, g0, g1, g2; bool live; };
-    BwIn nx;
-    // as field_bw_coop_kernel: every lane loads (index clamped), the incoming gradients are zeroed
-    // where the sample is out of range or on lanes h == 1 -- an idle wave's tile contributes zeros
-    auto fetch = [&](int64_t tile, BwIn& o) {
-        const int64_t s = tile * 32 + r;
-        const bool v = s < nn && h == 0;
-        const int64_t sc = max<int64_t>(0, min<int64_t>(s, nn - 1));
-        if constexpr (PLANAR) {
-            const uint32_t* Pp = reinterpret_cast<const uint32_t*>(feat);
-            uint32_t u[8];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                u[k] = Pp[(int64_t)(4 * h + k) * plane_stride + sc];
-                u[4 + k] = Pp[(int64_t)(8 + 4 * h + k) * plane_stride + sc];
-            }
-            o.I.x[0] = *reinterpret_cast<const half8*>(&u[0]);
-            o.I.x[1] = *reinterpret_cast<const half8*>(&u[4]);
-        } else {
-            const half8* row = reinterpret_cast<const half8*>(feat + sc * 32);
-            o.I.x[0] = row[h];
-            o.I.x[1] = row[2 + h];
-        }
-        o.I.d[0] = dirs[3 * sc]; o.I.d[1] = dirs[3 * sc + 1]; o.I.d[2] = dirs[3 * sc + 2];
-        o.gs = dL_dsigma[sc]; o.g0 = dL_drgb[3 * sc]; o.g1 = dL_drgb[3 * sc + 1]; o.g2 = dL_drgb[3 * sc + 2];
-        o.live = v;
-    };
-    auto zero_grads = [&](BwIn& o) {
-        o.gs = o.live ? o.gs : 0.0f;
-        o.g0 = o.live ? o.g0 : 0.0f;
-        o.g1 = o.live ? o.g1 : 0.0f;
-        o.g2 = o.live ? o.g2 : 0.0f;
-    };
-    if ((int64_t)blockIdx.x < groups) fetch(4 * (int64_t)blockIdx.x + wid, nx);
-    bool bad = false;
-    float l1a[4] = {0.f, 0.f, 0.f, 0.f}, l1b[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int64_t g = blockIdx.x; g < groups; g += gridDim.x) {
-        int opaque = 0;
-        asm volatile("" : "+s"(opaque));
-        const _Float16* lds = lds_base + opaque;
-        _Float16* area = lds_base + opaque + IMG_OFF / 2;
-        auto slot = [&](int u, int k) { return area + (u * COOP128_SLOTS + k) * TILE_HALFS; };
-        auto put2 = [&](_Float16* sl, const half8* v) {  // a 32-channel tile as two perm chunks
-            t_put(sl, lane, v[0], 0, true);
-            t_put(sl, lane, v[1], 4, true);
-        };
-        const int64_t tile = 4 * g + wid;
-        BwIn in = nx;
-        zero_grads(in);
-        fetch(4 * (g + (int64_t)gridDim.x) + wid, nx);  // (clamped past the end)
-        const bool valid = tile * 32 + r < nn;
-        FwdTile<W> T;
-        forward_tiles<W, false, 1>(lds, lane, &in.I, &valid, &T);
-        half8 dOb;
-        {
-            f32x16 dO = z;
-            dO[0] = in.g0 * S * T.rgb[0] * (1.0f - T.rgb[0]);
-            dO[1] = in.g1 * S * T.rgb[1] * (1.0f - T.rgb[1]);
-            dO[2] = in.g2 * S * T.rgb[2] * (1.0f - T.rgb[2]);
-            dOb = pack8<0, false>(dO);
-        }
-        //    dR2 = Wr3^T dO, masked by R2 > 0
-        half8 dr2p[MT][2];
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-            const f32x16 a = mfma(lds_frag(lds, G::B5 + mt, lane), dOb, z);
-            dr2p[mt][0] = relu_mask8(pack8<0, false>(a), T.r2[mt][0]);
-            dr2p[mt][1] = relu_mask8(pack8<8, false>(a), T.r2[mt][1]);
-        }
-        // ---- S1: dO, R2 -> dWr3[w]
-        t_put(slot(wid, 0), lane, dOb, 0, true);  // (channels 16..31 stale: rows 16..31 of dWr3, dropped)
-#pragma unroll
-        for (int i = 0; i < MT; ++i) put2(slot(wid, 1 + i), T.r2[i]);
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < 4; ++u) acc_tile(a_r3, s_get(slot(u, 0), lane), s_get(slot(u, 1 + wid), lane));
-        //    dR1 = Wr2^T dR2, masked by R1 > 0
-        half8 dr1p[MT][2];
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-            f32x16 a = z;
-#pragma unroll
-            for (int t = 0; t < MT; ++t)
-#pragma unroll
-                for (int k = 0; k < 2; ++k) a = mfma(lds_frag(lds, G::B4 + mt * G::KC + t * 2 + k, lane), dr2p[t][k], a);
-            dr1p[mt][0] = relu_mask8(pack8<0, false>(a), T.r1[mt][0]);
-            dr1p[mt][1] = relu_mask8(pack8<8, false>(a), T.r1[mt][1]);
-        }
-        __syncthreads();
-        // ---- S2a: dR2, R1[0..1] -> dWr2[w][0..1]
-#pragma unroll
-        for (int o = 0; o < MT; ++o) put2(slot(wid, o), dr2p[o]);
-        put2(slot(wid, 4), T.r1[0]);
-        put2(slot(wid, 5), T.r1[1]);
-        //    d[SH;h] = Wr1^T dR1 (rows 16..31 = dh) + TruncExp backward into h[0]
-        half8 dhb;
-        {
-            f32x16 dsh = z;
-#pragma unroll
-            for (int t = 0; t < MT; ++t)
-#pragma unroll
-                for (int k = 0; k < 2; ++k) dsh = mfma(lds_frag(lds, G::B3 + t * 2 + k, lane), dr1p[t][k], dsh);
-            const float dh0 = in.gs * S * __expf(fminf(fmaxf(T.h0, -15.0f), 15.0f));
-            dsh[8] = h == 0 ? dsh[8] + dh0 : dsh[8];
-            dhb = pack8<8, false>(dsh);
-            if constexpr (DDIRS) {  // rows 0..15 = dL/dSH: the chain rule to the sample's direction
-                // (the direction is read again: keeping the forward's copy live costs registers)
-                __builtin_amdgcn_sched_barrier(0);
-                const int64_t s = tile * 32 + r, sc = max<int64_t>(0, min<int64_t>(s, nn - 1));
-                const float dv[3] = {dirs[3 * sc], dirs[3 * sc + 1], dirs[3 * sc + 2]};
-                float gd[3];
-                sh4_bw_dir(dsh, h, invS, dv, gd);
-                if (h == 0 && s < nn) {
-                    bad |= !(isfinite(gd[0]) && isfinite(gd[1]) && isfinite(gd[2]));
-                    dL_ddirs[3 * s] = gd[0]; dL_ddirs[3 * s + 1] = gd[1]; dL_ddirs[3 * s + 2] = gd[2];
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const SOp d = s_get(slot(u, wid), lane);
-            acc_tile(a_r2[0], d, s_get(slot(u, 4), lane));
-            acc_tile(a_r2[1], d, s_get(slot(u, 5), lane));
-        }
-        //    dY1 = W2^T dh, masked by Y1 > 0; dX = W1^T dY1
-        half8 dy1p[2][2];
-        f32x16 dx = z;
-        {
-            const f32x16 a0 = mfma(lds_frag(lds, G::B2 + 0, lane), dhb, z);
-            const f32x16 a1 = mfma(lds_frag(lds, G::B2 + 1, lane), dhb, z);
-            dy1p[0][0] = relu_mask8(pack8<0, false>(a0), T.y1[0][0]);
-            dy1p[0][1] = relu_mask8(pack8<8, false>(a0), T.y1[0][1]);
-            dy1p[1][0] = relu_mask8(pack8<0, false>(a1), T.y1[1][0]);
-            dy1p[1][1] = relu_mask8(pack8<8, false>(a1), T.y1[1][1]);
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int k = 0; k < 2; ++k) dx = mfma(lds_frag(lds, G::B1 + t * 2 + k, lane), dy1p[t][k], dx);
-        }
-        __syncthreads();
-        // ---- S2b: R1[2..3] over R1[0..1] -> dWr2[w][2..3] (dR2 still in slots 0..3)
-        put2(slot(wid, 4), T.r1[2]);
-        put2(slot(wid, 5), T.r1[3]);
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const SOp d = s_get(slot(u, wid), lane);
-            acc_tile(a_r2[2], d, s_get(slot(u, 4), lane));
-            acc_tile(a_r2[3], d, s_get(slot(u, 5), lane));
-        }
-        // dX = W1^T dY1 -> global fp32 (features (i&3)+8(i>>2)+4h), this wave's own tile
-        {
-            const int64_t s = tile * 32 + r;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float4 o = make_float4(dx[4 * q] * invS, dx[4 * q + 1] * invS, dx[4 * q + 2] * invS, dx[4 * q + 3] * invS);
-                bad |= !(isfinite(o.x) && isfinite(o.y) && isfinite(o.z) && isfinite(o.w));
-                if (s < nn) reinterpret_cast<float4*>(dL_dfeat + s * 32)[2 * q + h] = o;
-                l1a[q] += fabsf(o.x) + fabsf(o.y);
-                l1b[q] += fabsf(o.z) + fabsf(o.w);
-            }
-        }
-        __syncthreads();
-        // ---- S3: dR1, [SH;h] -> dWr1[w]
-#pragma unroll
-        for (int o = 0; o < MT; ++o) put2(slot(wid, o), dr1p[o]);
-        t_put(slot(wid, 4), lane, T.sh, 0, false);
-        t_put(slot(wid, 4), lane, T.hb, 4, true);
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < 4; ++u) acc_tile(a_r1, s_get(slot(u, wid), lane), s_get(slot(u, 4), lane));
-        __syncthreads();
-        // ---- S4: dh, Y1 -> dW2 (waves 0, 1)
-        t_put(slot(wid, 0), lane, dhb, 0, true);  // (channels 16..31 stale: rows of dW2 dropped)
-        put2(slot(wid, 1), T.y1[0]);
-        put2(slot(wid, 2), T.y1[1]);
-        __syncthreads();
-        if (wid < 2) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) acc_tile(a_x, s_get(slot(u, 0), lane), s_get(slot(u, 1 + wid), lane));
-        }
-        __syncthreads();
-        // ---- S5: dY1, X -> dW1 (waves 2, 3)
-        put2(slot(wid, 0), dy1p[0]);
-        put2(slot(wid, 1), dy1p[1]);
-        t_put(slot(wid, 2), lane, T.x[0], 0, false);
-        t_put(slot(wid, 2), lane, T.x[1], 4, false);
-        __syncthreads();
-        if (wid >= 2) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) acc_tile(a_x, s_get(slot(u, wid - 2), lane), s_get(slot(u, 2), lane));
-        }
-        __syncthreads();  // the images are rewritten by the next group's S1
-    }
-    if (nonfinite && __any(bad) && lane == 0) atomicOr(nonfinite, 1);
-
-    // ---- epilogue: each tile stored by its owner wave (disjoint, every entry once) -> one slab row
-    float* row = slab + (int64_t)blockIdx.x * G::N_DW;
-    {
-        constexpr int N_IMG = G::N_DW;
-        static_assert((size_t)N_IMG * 4 + 64 <= IMG_OFF, "reduction image must fit the fragment area");
-        xdl_drain();
-        __syncthreads();
-        float* img = reinterpret_cast<float*>(smem);
-        float* l1_part = img + N_IMG;
-        if (threadIdx.x < 16) l1_part[threadIdx.x] = 0.0f;
-        __syncthreads();
-        if (level_l1) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                float a = l1a[q], b = l1b[q];
-#pragma unroll
-                for (int off = 16; off > 0; off >>= 1) { a += __shfl_xor(a, off, 64); b += __shfl_xor(b, off, 64); }
-                if (r == 0) { atomicAdd(l1_part + 4 * q + 2 * h, a); atomicAdd(l1_part + 4 * q + 2 * h + 1, b); }
-            }
-        }
-        dw_add32(img + oR3, a_r3, 0, wid, 16, W, lane, true);
-        dw_add32(img + oR1, a_r1, wid, 0, W, 32, lane, true);
-#pragma unroll
-        for (int i = 0; i < MT; ++i) dw_add32(img + oR2, a_r2[i], wid, i, W, W, lane, true);
-        if (wid < 2) dw_add32(img + 64 * 32, a_x, 0, wid, 16, 64, lane, true);
-        else dw_add32(img, a_x, wid - 2, 0, 64, 32, lane, true);
         __syncthreads();
         bool rbad = false;  // a non-finite weight-gradient partial (see slab_row_flag)
         for (int i = threadIdx.x; i < G::N_DW; i += blockDim.x) {
@@ -951,16 +744,19 @@ __global__ __launch_bounds__(256) void slab_reduce_kernel(const float* __restric
     }
 }
 
-constexpr int BW_BLOCKS = 256;  // one workgroup per CU (persistent)
-
-// slab rows: W = 64 field_bw_coop_kernel (two workgroups per CU), W = 128 field_bw_coop128_kernel (one)
-int bw_rows(int w) { return w == 64 ? COOP_BLOCKS : BW_BLOCKS; }
-
 bool width_ok(int w) { return w == 64 || w == 128; }
 
 int bad_width(int w) {
     mfn_set_error("field: rgb_width=%d unsupported (this build: 64 or 128)", w);
     return MFN_ERR_INVALID;
+}
+
+// f(std::integral_constant<int, W>{}) for a width that width_ok accepted: the one place that picks
+// between the two instantiations (as mlp_dispatch in mlp.hip)
+template <typename F>
+auto width_dispatch(int rgb_width, F&& f) -> decltype(f(std::integral_constant<int, 64>{})) {
+    if (rgb_width == 64) return f(std::integral_constant<int, 64>{});
+    return f(std::integral_constant<int, 128>{});
 }
 
 template <typename TP, int W>
@@ -987,19 +783,18 @@ void launch_fw(const void* feat, int64_t ps, const float* dirs, int64_t n, const
                            (const _Float16*)packed, sigma, rgb, nullptr, nullptr);
 }
 
-// the cooperative backward of width W (its kernel pair, workgroups = slab rows, LDS), then the slab fold
-// (unless deferred: grad_xyz null, mfnerf_field_bw_reduce folds the slab later)
+// the cooperative backward of width W (row-major and planar kernels; workgroups = slab rows and LDS
+// from CoopGeo), then the slab fold (unless deferred: grad_xyz null, mfnerf_field_bw_reduce folds
+// the slab later)
 // DDIRS (mfnerf_field_bw_inputs): the kernels' direction-gradient instantiation, writing dL_ddirs
-template <int W, bool DDIRS = false>
+template <int W, bool DDIRS>
 int launch_bw(const void* feat, int64_t ps, const float* dirs, int64_t n, const int32_t* n_dev, const void* packed,
               const float* dL_dsigma, const float* dL_drgb, float grad_scale, const float* scale_dev, float* dL_dfeat,
               float* grad_xyz, float* grad_rgb, void* workspace, int32_t* nonfinite, float* level_l1,
-              mfnerf_stream_t stream, float* dL_ddirs = nullptr) {
-    using K = decltype(&field_bw_coop_kernel<false, DDIRS>);
-    constexpr K k0 = W == 64 ? field_bw_coop_kernel<false, DDIRS> : field_bw_coop128_kernel<false, DDIRS>;
-    constexpr K k1 = W == 64 ? field_bw_coop_kernel<true, DDIRS> : field_bw_coop128_kernel<true, DDIRS>;
-    constexpr size_t lds = W == 64 ? COOP_LDS : COOP128_LDS;
-    const int rows = bw_rows(W);
+              mfnerf_stream_t stream, float* dL_ddirs) {
+    constexpr auto k0 = field_bw_coop_kernel<W, false, DDIRS>, k1 = field_bw_coop_kernel<W, true, DDIRS>;
+    constexpr size_t lds = CoopGeo<W>::LDS;
+    constexpr int rows = CoopGeo<W>::BLOCKS;
     static const hipError_t attr = [] {
         const hipError_t a0 = hipFuncSetAttribute(reinterpret_cast<const void*>(k0),
                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1038,15 +833,11 @@ int field_bw_impl(const void* feat_f16, int64_t feat_plane_stride, const float* 
     }
     int32_t* nonfinite = amp ? &amp->nonfinite : nullptr;
     const float* scale_dev = grad_scale == 0.0f ? &amp->scale : nullptr;
-    int st;
-    if (rgb_width == 128)
-        st = launch_bw<128, DDIRS>(feat_f16, feat_plane_stride, dirs, n, n_dev, packed, dL_dsigma, dL_drgb, grad_scale,
-                                   scale_dev, dL_dfeat, grad_xyz, grad_rgb, workspace, nonfinite, level_l1, stream,
-                                   dL_ddirs);
-    else
-        st = launch_bw<64, DDIRS>(feat_f16, feat_plane_stride, dirs, n, n_dev, packed, dL_dsigma, dL_drgb, grad_scale,
-                                  scale_dev, dL_dfeat, grad_xyz, grad_rgb, workspace, nonfinite, level_l1, stream,
-                                  dL_ddirs);
+    const int st = width_dispatch(rgb_width, [&](auto w) {
+        return launch_bw<decltype(w)::value, DDIRS>(feat_f16, feat_plane_stride, dirs, n, n_dev, packed, dL_dsigma,
+                                                    dL_drgb, grad_scale, scale_dev, dL_dfeat, grad_xyz, grad_rgb,
+                                                    workspace, nonfinite, level_l1, stream, dL_ddirs);
+    });
     if (st != MFN_OK) return st;
     return mfn_check_launch(DDIRS ? "field_bw_inputs" : "field_bw");
 }
@@ -1056,17 +847,15 @@ int field_bw_impl(const void* feat_f16, int64_t feat_plane_stride, const float* 
 extern "C" {
 
 int64_t mfnerf_field_packed_bytes(int rgb_width) {
-    if (rgb_width == 64) return (int64_t)Geo<64>::N * FRAG_HALFS * 2;
-    if (rgb_width == 128) return (int64_t)Geo<128>::N * FRAG_HALFS * 2;
-    return -1;
+    if (!width_ok(rgb_width)) return -1;
+    return width_dispatch(rgb_width, [](auto w) { return (int64_t)Geo<decltype(w)::value>::N * FRAG_HALFS * 2; });
 }
 
 int mfnerf_field_pack_weights(const float* params_xyz, const float* params_rgb, int rgb_width, void* packed,
                               mfnerf_stream_t stream) {
     if (!width_ok(rgb_width)) return bad_width(rgb_width);
     if (!params_xyz || !params_rgb || !packed) { mfn_set_error("field_pack_weights: null pointer"); return MFN_ERR_INVALID; }
-    if (rgb_width == 64) launch_pack<float, 64>(params_xyz, params_rgb, packed, stream);
-    else launch_pack<float, 128>(params_xyz, params_rgb, packed, stream);
+    width_dispatch(rgb_width, [&](auto w) { launch_pack<float, decltype(w)::value>(params_xyz, params_rgb, packed, stream); });
     return mfn_check_launch("field_pack_weights");
 }
 
@@ -1084,8 +873,7 @@ int mfnerf_field_pack_weights_f16(const void* params_xyz_f16, const void* params
     if (!params_xyz_f16 || !params_rgb_f16 || !packed) { mfn_set_error("field_pack_weights_f16: null pointer"); return MFN_ERR_INVALID; }
     const _Float16* px = (const _Float16*)params_xyz_f16;
     const _Float16* pr = (const _Float16*)params_rgb_f16;
-    if (rgb_width == 64) launch_pack<_Float16, 64>(px, pr, packed, stream);
-    else launch_pack<_Float16, 128>(px, pr, packed, stream);
+    width_dispatch(rgb_width, [&](auto w) { launch_pack<_Float16, decltype(w)::value>(px, pr, packed, stream); });
     return mfn_check_launch("field_pack_weights_f16");
 }
 
@@ -1098,8 +886,9 @@ int mfnerf_field_fw(const void* feat_f16, int64_t feat_plane_stride, const float
     if (!feat_f16 || !packed || !sigma || (!density_only && (!dirs || !rgb))) {
         mfn_set_error("field_fw: null pointer"); return MFN_ERR_INVALID;
     }
-    if (rgb_width == 64) launch_fw<64>(feat_f16, feat_plane_stride, dirs, n, n_dev, packed, density_only, sigma, rgb, stream);
-    else launch_fw<128>(feat_f16, feat_plane_stride, dirs, n, n_dev, packed, density_only, sigma, rgb, stream);
+    width_dispatch(rgb_width, [&](auto w) {
+        launch_fw<decltype(w)::value>(feat_f16, feat_plane_stride, dirs, n, n_dev, packed, density_only, sigma, rgb, stream);
+    });
     return mfn_check_launch("field_fw");
 }
 
@@ -1116,20 +905,24 @@ int mfnerf_field_fw_density_scatter(const void* feat_f16, int64_t feat_plane_str
         mfn_set_error("field_fw_density_scatter: null pointer");
         return MFN_ERR_INVALID;
     }
-    if (rgb_width == 64) launch_fw<64>(feat_f16, feat_plane_stride, nullptr, n, n_dev, packed, 1, sigma, nullptr, stream, cell_idx, tmp);
-    else launch_fw<128>(feat_f16, feat_plane_stride, nullptr, n, n_dev, packed, 1, sigma, nullptr, stream, cell_idx, tmp);
+    width_dispatch(rgb_width, [&](auto w) {
+        launch_fw<decltype(w)::value>(feat_f16, feat_plane_stride, nullptr, n, n_dev, packed, 1, sigma, nullptr, stream, cell_idx, tmp);
+    });
     return mfn_check_launch("field_fw_density_scatter");
 }
 
 int mfnerf_field_bw_slab_rows(int rgb_width) {
-    return rgb_width == 64 ? bw_rows(64) : rgb_width == 128 ? BW_BLOCKS : -1;
+    if (!width_ok(rgb_width)) return -1;
+    return width_dispatch(rgb_width, [](auto w) { return CoopGeo<decltype(w)::value>::BLOCKS; });
 }
 
 int64_t mfnerf_field_bw_workspace(int64_t n, int rgb_width) {
     (void)n;
-    if (rgb_width == 64) return (int64_t)bw_rows(64) * Geo<64>::N_DW * 4;
-    if (rgb_width == 128) return (int64_t)BW_BLOCKS * Geo<128>::N_DW * 4;
-    return -1;
+    if (!width_ok(rgb_width)) return -1;
+    return width_dispatch(rgb_width, [](auto w) {
+        constexpr int W = decltype(w)::value;
+        return (int64_t)CoopGeo<W>::BLOCKS * Geo<W>::N_DW * 4;
+    });
 }
 
 int mfnerf_field_bw(const void* feat_f16, int64_t feat_plane_stride, const float* dirs, int64_t n,
@@ -1154,12 +947,11 @@ static int field_bw_fold(int rgb_width, const void* workspace, float* grad_xyz, 
                          int store, mfnerf_stream_t stream) {
     if (!width_ok(rgb_width)) return bad_width(rgb_width);
     if (!workspace || !grad_xyz || !grad_rgb) { mfn_set_error("field_bw_reduce: null pointer"); return MFN_ERR_INVALID; }
-    if (rgb_width == 64)
-        hipLaunchKernelGGL(slab_reduce_kernel<64>, dim3((Geo<64>::N_DW + 63) / 64), dim3(256), 0, stream,
-                           (const float*)workspace, bw_rows(64), grad_xyz, grad_rgb, nonfinite, store);
-    else
-        hipLaunchKernelGGL(slab_reduce_kernel<128>, dim3((Geo<128>::N_DW + 63) / 64), dim3(256), 0, stream,
-                           (const float*)workspace, BW_BLOCKS, grad_xyz, grad_rgb, nonfinite, store);
+    width_dispatch(rgb_width, [&](auto w) {
+        constexpr int W = decltype(w)::value;
+        hipLaunchKernelGGL(slab_reduce_kernel<W>, dim3((Geo<W>::N_DW + 63) / 64), dim3(256), 0, stream,
+                           (const float*)workspace, CoopGeo<W>::BLOCKS, grad_xyz, grad_rgb, nonfinite, store);
+    });
     return mfn_check_launch("field_bw_reduce");
 }
 
