@@ -131,6 +131,19 @@ int mfnerf_composite_train_fused(const float* sigmas, const float* rgbs, const f
                                  float* ws, float* dL_drgb, float* dL_dopacity, float* dL_dsigmas, float* dL_drgbs,
                                  float* loss_partials, mfnerf_stream_t stream);
 
+/* mfnerf_composite_train_fused with the background colour read from device memory: bg (3 f32,
+ * device, required) in place of bg_r, bg_g, bg_b.  For --random_bg (rendering.py:153-161: one random
+ * colour per training batch, blended into the prediction only), where the colour is drawn on the device
+ * and a captured graph would freeze scalar arguments.  The same kernel, specialised at compile time;
+ * the three values are read once per ray before the sample loop, the arithmetic and its order are
+ * those of the scalar form: with equal values every output is bit-identical. */
+int mfnerf_composite_train_fused_bg(const float* sigmas, const float* rgbs, const float* deltas, const float* ts,
+                                    const int64_t* rays_a, int64_t n_rays, int64_t n_samples, float T_threshold,
+                                    const float* target, int64_t n_mean, float lambda_opacity, const float* bg,
+                                    int64_t* total_samples, float* opacity, float* depth, float* rgb, float* ws,
+                                    float* dL_drgb, float* dL_dopacity, float* dL_dsigmas, float* dL_drgbs,
+                                    float* loss_partials, mfnerf_stream_t stream);
+
 /* vren.composite_test_fw (binding.cpp:176-201, volumerendering.cu:205-285).  sigmas (n_alive,N_samples),
  * rgbs (n_alive,N_samples,3), deltas, ts (n_alive,N_samples); in place on alive_indices, opacity,
  * depth, rgb (indexed by ray). */
@@ -159,6 +172,13 @@ int mfnerf_distortion_loss_bw(const float* dL_dloss, const float* ws_incl, const
 int mfnerf_nerf_loss(const float* rgb, const float* opacity, const float* target, int64_t n_rays, int64_t n_mean,
                      float lambda_opacity, float bg_r, float bg_g, float bg_b, float* dL_drgb, float* dL_dopacity,
                      float* loss_sum, mfnerf_stream_t stream);
+
+/* mfnerf_nerf_loss with the background colour read from device memory (bg: 3 f32, device, required;
+ * --random_bg, rendering.py:153-161), once per thread; the same kernel specialised at compile time,
+ * bit-identical to the scalar form for equal values. */
+int mfnerf_nerf_loss_bg(const float* rgb, const float* opacity, const float* target, int64_t n_rays, int64_t n_mean,
+                        float lambda_opacity, const float* bg, float* dL_drgb, float* dL_dopacity, float* loss_sum,
+                        mfnerf_stream_t stream);
 
 /* ---------------------------------------------------------------- grid encoding (tcnn HashGrid / MF) */
 
@@ -555,6 +575,19 @@ int mfnerf_sample_rays_prep_idx(const float* images, const float* poses, const f
                                 int64_t hw, int64_t n_rays, int same_image, uint64_t seed, uint64_t* call, float* out,
                                 const float* center, const float* half_size, float near, float* hits_t, float* noise,
                                 int32_t* img_idx, int32_t* pix_idx, mfnerf_stream_t stream);
+
+/* mfnerf_sample_rays_prep_idx (img_idx / pix_idx optional, each may be null) that also draws the
+ * batch's random background colour (--random_bg, rendering.py:153-161: one torch.rand(3) per render()
+ * call) into bg (3 f32, device, required), in the same launch, so the colour belongs to the batch it
+ * was drawn with.  Component c = (mix32(key + c * 0x9E3779B97F4A7C15) >> 8) * 2^-24, U[0,1) with 24
+ * bits, key = splitmix64(splitmix64(seed ^ 0xA0761D6478BD642F) ^ call[0]) with call[0] read before the
+ * launch advances it (a stream constant of its own): a function of seed and call[0] alone, not of
+ * n_rays or same_image.  One thread stores it.  Every other output has the bits of
+ * mfnerf_sample_rays_prep_idx for the same seed and counter. */
+int mfnerf_sample_rays_prep_bg(const float* images, const float* poses, const float* directions, int64_t n_img,
+                               int64_t hw, int64_t n_rays, int same_image, uint64_t seed, uint64_t* call, float* out,
+                               const float* center, const float* half_size, float near, float* hits_t, float* noise,
+                               int32_t* img_idx, int32_t* pix_idx, float* bg, mfnerf_stream_t stream);
 
 /* ---------------------------------------------------------------- camera-pose refinement */
 

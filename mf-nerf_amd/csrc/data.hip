@@ -41,7 +41,18 @@ struct MarchPrep {
     float near;
     float* hits_t;  // (n_rays, 2), null: no prologue
     float* noise;   // (n_rays)
+    float* bg;      // (3) the batch's background colour (--random_bg), null: none
 };
+
+// The batch's random background colour (rendering.py:153-161: one torch.rand(3) per render() call):
+// component c ~ U[0,1) with 24 random bits from (seed, call) alone -- not from n_rays, the sampling
+// strategy or the thread that stores it -- on a stream of its own beside the two of draw_ray.
+__device__ __forceinline__ void draw_bg(uint64_t seed, const uint64_t* __restrict__ call, float* __restrict__ bg) {
+    const uint64_t key = splitmix64(splitmix64(seed ^ 0xA0761D6478BD642Full) ^ (call ? *call : 0ull));
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+        bg[c] = (float)(mix32(key + (uint64_t)c * 0x9E3779B97F4A7C15ull) >> 8) * (1.0f / 16777216.0f);
+}
 
 // one ray of the batch: image + pixel draw, rays, rgb, and optionally the march prologue
 __device__ __forceinline__ void draw_ray(int64_t r, const float* __restrict__ images, const float* __restrict__ poses,
@@ -105,6 +116,9 @@ __global__ void sample_rays_kernel(const float* __restrict__ images, const float
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r < n_rays) draw_ray(r, images, poses, directions, n_img, hw, n_rays, same_image, seed, call, out, img_idx,
                              pix_idx, prep);
+    // one thread of the launch (it exists: n_rays > 0) stores the colour; like every draw it reads *call
+    // before its workgroup's barrier below, so before the last workgroup can advance the counter
+    if (r == 0 && prep.bg) draw_bg(seed, call, prep.bg);
     if (call) {
         // every thread of the block has read *call above; the last block to arrive advances it
         __syncthreads();
@@ -129,7 +143,7 @@ extern "C" int mfnerf_sample_rays(const float* images, const float* poses, const
     }
     if (n_rays == 0) return MFN_OK;
     if (!images || !poses || !directions || !out) { mfn_set_error("sample_rays: null pointer"); return MFN_ERR_INVALID; }
-    const MarchPrep none{nullptr, nullptr, 0.0f, nullptr, nullptr};
+    const MarchPrep none{nullptr, nullptr, 0.0f, nullptr, nullptr, nullptr};
     hipLaunchKernelGGL(sample_rays_kernel, dim3((unsigned)div_up<int64_t>(n_rays, 256)), dim3(256), 0, stream, images,
                        poses, directions, n_img, hw, n_rays, same_image, seed, call, out, img_idx, pix_idx, none);
     return mfn_check_launch("sample_rays");
@@ -148,7 +162,7 @@ extern "C" int mfnerf_sample_rays_prep(const float* images, const float* poses, 
         mfn_set_error("sample_rays_prep: null pointer");
         return MFN_ERR_INVALID;
     }
-    const MarchPrep prep{center, half_size, near, hits_t, noise};
+    const MarchPrep prep{center, half_size, near, hits_t, noise, nullptr};
     hipLaunchKernelGGL(sample_rays_kernel, dim3((unsigned)div_up<int64_t>(n_rays, 256)), dim3(256), 0, stream, images,
                        poses, directions, n_img, hw, n_rays, same_image, seed, call, out, (int32_t*)nullptr,
                        (int32_t*)nullptr, prep);
@@ -169,8 +183,28 @@ extern "C" int mfnerf_sample_rays_prep_idx(const float* images, const float* pos
         mfn_set_error("sample_rays_prep_idx: null pointer");
         return MFN_ERR_INVALID;
     }
-    const MarchPrep prep{center, half_size, near, hits_t, noise};
+    const MarchPrep prep{center, half_size, near, hits_t, noise, nullptr};
     hipLaunchKernelGGL(sample_rays_kernel, dim3((unsigned)div_up<int64_t>(n_rays, 256)), dim3(256), 0, stream, images,
                        poses, directions, n_img, hw, n_rays, same_image, seed, call, out, img_idx, pix_idx, prep);
     return mfn_check_launch("sample_rays_prep_idx");
+}
+
+extern "C" int mfnerf_sample_rays_prep_bg(const float* images, const float* poses, const float* directions,
+                                          int64_t n_img, int64_t hw, int64_t n_rays, int same_image, uint64_t seed,
+                                          uint64_t* call, float* out, const float* center, const float* half_size,
+                                          float near, float* hits_t, float* noise, int32_t* img_idx,
+                                          int32_t* pix_idx, float* bg, mfnerf_stream_t stream) {
+    if (n_img <= 0 || hw <= 0 || n_rays < 0 || n_img > 0x7fffffff || hw > 0x7fffffff) {
+        mfn_set_error("sample_rays_prep_bg: bad sizes");
+        return MFN_ERR_INVALID;
+    }
+    if (n_rays == 0) return MFN_OK;
+    if (!images || !poses || !directions || !out || !center || !half_size || !hits_t || !noise || !bg) {
+        mfn_set_error("sample_rays_prep_bg: null pointer");
+        return MFN_ERR_INVALID;
+    }
+    const MarchPrep prep{center, half_size, near, hits_t, noise, bg};
+    hipLaunchKernelGGL(sample_rays_kernel, dim3((unsigned)div_up<int64_t>(n_rays, 256)), dim3(256), 0, stream, images,
+                       poses, directions, n_img, hw, n_rays, same_image, seed, call, out, img_idx, pix_idx, prep);
+    return mfn_check_launch("sample_rays_prep_bg");
 }

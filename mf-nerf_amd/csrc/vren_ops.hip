@@ -609,6 +609,24 @@ __global__ __launch_bounds__(256) void composite_bw_wave_kernel(
     }
 }
 
+// The loss's background colour (rendering.py:153-161) as the loss-carrying kernels take it: three
+// kernel arguments (a fixed colour: white on synthetic scenes, black on real ones), or three floats in
+// device memory (--random_bg: the colour is drawn on the device for each batch, and a captured graph
+// freezes its scalar arguments).  A template parameter of the kernels chooses at compile time:
+// DEV_BG = false keeps the parameter list (float, float, float) and so, instruction for instruction, the
+// code the kernels had before the option existed (a struct of three floats, or the body behind a thin
+// kernel, each reordered it); DEV_BG = true takes (const float*, -, -) and reads the three values once,
+// before any sample.  Both feed the same arithmetic in the same order.
+struct BgUnused {};
+template <bool DEV_BG> struct BgParam { using first = float; using rest = float; };
+template <> struct BgParam<true> { using first = const float*; using rest = BgUnused; };
+template <bool DEV_BG>
+__device__ __forceinline__ void bg_fetch(typename BgParam<DEV_BG>::first a0, typename BgParam<DEV_BG>::rest a1,
+                                         typename BgParam<DEV_BG>::rest a2, float& b0, float& b1, float& b2) {
+    if constexpr (DEV_BG) { b0 = a0[0]; b1 = a0[1]; b2 = a0[2]; }
+    else { b0 = a0; b1 = a1; b2 = a2; }
+}
+
 // Fused training compositing for the default loss (no distortion term): composite_train_fw ->
 // background blend + NeRFLoss and its gradient -> composite_train_bw with dL/ddepth = 0 and
 // dL/dws = 0, one wave per ray, one launch.  Pass 1 is composite_fw_wave_kernel's loop and also
@@ -616,11 +634,13 @@ __global__ __launch_bounds__(256) void composite_bw_wave_kernel(
 // T back (same lane, same address) instead of re-walking the transmittance chain, so the result is
 // bit-identical to the three separate kernels (the dropped terms are exact zeros).  The loss value
 // is written as one partial sum per workgroup of 4 rays (plain stores: no zeroing, no atomics).
-
+// DEV_BG: the background colour is three floats in device memory, read once per ray before pass 1.
+template <bool DEV_BG>
 __global__ __launch_bounds__(256) void composite_fused_wave_kernel(
     const float* __restrict__ sigmas, const float* __restrict__ rgbs, const float* __restrict__ deltas,
     const float* __restrict__ ts, const int64_t* __restrict__ rays_a, int64_t n_rays, float T_thr,
-    const float* __restrict__ target, int64_t n_mean, float lambda_o, float bg0, float bg1, float bg2,
+    const float* __restrict__ target, int64_t n_mean, float lambda_o, typename BgParam<DEV_BG>::first bg0,
+    typename BgParam<DEV_BG>::rest bg1, typename BgParam<DEV_BG>::rest bg2,
     int64_t* __restrict__ total_samples, float* __restrict__ opacity, float* __restrict__ depth,
     float* __restrict__ rgb, float* __restrict__ ws, float* __restrict__ dL_drgb, float* __restrict__ dL_dop,
     float* __restrict__ dL_dsigmas, float* __restrict__ dL_drgbs, float* __restrict__ loss_part) {
@@ -632,6 +652,8 @@ __global__ __launch_bounds__(256) void composite_fused_wave_kernel(
         const int64_t ray = rays_a[3 * n], start = rays_a[3 * n + 1];
         const int N = (int)rays_a[3 * n + 2];
         const float tg[3] = {target[3 * ray], target[3 * ray + 1], target[3 * ray + 2]};
+        float b0, b1, b2;
+        bg_fetch<DEV_BG>(bg0, bg1, bg2, b0, b1, b2);
         // ---- pass 1: forward (composite_fw_wave_kernel)
         float T = 1.0f, R = 0.f, G = 0.f, B = 0.f, D = 0.f, O = 0.f;
         int total = N;
@@ -665,7 +687,7 @@ __global__ __launch_bounds__(256) void composite_fused_wave_kernel(
         R = wave_sum(R); G = wave_sum(G); B = wave_sum(B); D = wave_sum(D); O = wave_sum(O);
         // ---- loss (nerf_loss_kernel, same expression order), wave-uniform
         const float inv3n = 1.0f / (3.0f * (float)n_mean), invn = 1.0f / (float)n_mean;
-        const float bg[3] = {bg0, bg1, bg2}, col[3] = {R, G, B};
+        const float bg[3] = {b0, b1, b2}, col[3] = {R, G, B};
         float gcol[3], dop = 0.0f;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
@@ -796,17 +818,20 @@ __global__ void distortion_bw_kernel(const float* __restrict__ dL_dloss, const f
 // ------------------------------------------------------------------ NeRF loss (losses.py:47-60, train.py:178)
 // pred = rgb + bg*(1-opacity) (rendering.py:153-161); loss = mean((pred-gt)^2) + lambda*mean(-o ln o),
 // o = opacity + 1e-10.  Writes dL/drgb, dL/dopacity of that scalar and accumulates it into loss_sum.
+template <bool DEV_BG>
 __global__ void nerf_loss_kernel(const float* __restrict__ rgb, const float* __restrict__ opacity,
                                  const float* __restrict__ gt, int64_t n_rays, int64_t n_mean, float lambda_o,
-                                 float bg0, float bg1,
-                                 float bg2, float* __restrict__ dL_drgb, float* __restrict__ dL_dop,
-                                 float* __restrict__ loss_sum) {
+                                 typename BgParam<DEV_BG>::first bg0, typename BgParam<DEV_BG>::rest bg1,
+                                 typename BgParam<DEV_BG>::rest bg2, float* __restrict__ dL_drgb,
+                                 float* __restrict__ dL_dop, float* __restrict__ loss_sum) {
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     float l = 0.0f;
     if (r < n_rays) {
         const float op = opacity[r];
         const float inv3n = 1.0f / (3.0f * (float)n_mean), invn = 1.0f / (float)n_mean;
-        const float bg[3] = {bg0, bg1, bg2};
+        float b0, b1, b2;
+        bg_fetch<DEV_BG>(bg0, bg1, bg2, b0, b1, b2);
+        const float bg[3] = {b0, b1, b2};
         float dop = 0.0f;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
@@ -826,6 +851,49 @@ __global__ void nerf_loss_kernel(const float* __restrict__ rgb, const float* __r
 }
 
 inline unsigned blocks_for(int64_t n, int b) { return (unsigned)div_up<int64_t>(n, b); }
+
+// the two forms of mfnerf_composite_train_fused / mfnerf_nerf_loss: one validation, one launch
+template <bool DEV_BG>
+int composite_train_fused_launch(const char* what, const float* sigmas, const float* rgbs, const float* deltas,
+                                 const float* ts, const int64_t* rays_a, int64_t n_rays, int64_t n_samples,
+                                 float T_threshold, const float* target, int64_t n_mean, float lambda_opacity,
+                                 typename BgParam<DEV_BG>::first bg0, typename BgParam<DEV_BG>::rest bg1,
+                                 typename BgParam<DEV_BG>::rest bg2, int64_t* total_samples, float* opacity,
+                                 float* depth, float* rgb, float* ws, float* dL_drgb, float* dL_dopacity,
+                                 float* dL_dsigmas, float* dL_drgbs, float* loss_partials, mfnerf_stream_t stream) {
+    if (n_rays < 0 || n_samples < 0 || n_mean < 0 || (n_mean > 0 && n_mean < n_rays)) {
+        mfn_set_error("%s: bad sizes", what); return MFN_ERR_INVALID;
+    }
+    if (n_mean == 0) n_mean = n_rays;
+    if (n_rays == 0) return MFN_OK;
+    if (!rays_a || !target || !total_samples || !opacity || !depth || !rgb || !dL_drgb || !dL_dopacity ||
+        (n_samples > 0 && (!sigmas || !rgbs || !deltas || !ts || !ws || !dL_dsigmas || !dL_drgbs))) {
+        mfn_set_error("%s: null pointer", what); return MFN_ERR_INVALID;
+    }
+    hipLaunchKernelGGL(composite_fused_wave_kernel<DEV_BG>, dim3(blocks_for(n_rays, 4)), dim3(256), 0, stream, sigmas,
+                       rgbs, deltas, ts, rays_a, n_rays, T_threshold, target, n_mean, lambda_opacity, bg0, bg1, bg2,
+                       total_samples, opacity, depth, rgb, ws, dL_drgb, dL_dopacity, dL_dsigmas, dL_drgbs,
+                       loss_partials);
+    return mfn_check_launch(what);
+}
+
+template <bool DEV_BG>
+int nerf_loss_launch(const char* what, const float* rgb, const float* opacity, const float* target, int64_t n_rays,
+                     int64_t n_mean, float lambda_opacity, typename BgParam<DEV_BG>::first bg0,
+                     typename BgParam<DEV_BG>::rest bg1, typename BgParam<DEV_BG>::rest bg2, float* dL_drgb,
+                     float* dL_dopacity, float* loss_sum, mfnerf_stream_t stream) {
+    if (n_rays < 0 || n_mean < 0 || (n_mean > 0 && n_mean < n_rays)) {
+        mfn_set_error("%s: bad size", what); return MFN_ERR_INVALID;
+    }
+    if (n_mean == 0) n_mean = n_rays;
+    if (n_rays == 0) return MFN_OK;
+    if (!rgb || !opacity || !target || !dL_drgb || !dL_dopacity) {
+        mfn_set_error("%s: null pointer", what); return MFN_ERR_INVALID;
+    }
+    hipLaunchKernelGGL(nerf_loss_kernel<DEV_BG>, dim3(blocks_for(n_rays, 256)), dim3(256), 0, stream, rgb, opacity,
+                       target, n_rays, n_mean, lambda_opacity, bg0, bg1, bg2, dL_drgb, dL_dopacity, loss_sum);
+    return mfn_check_launch(what);
+}
 
 }  // namespace
 
@@ -975,20 +1043,23 @@ int mfnerf_composite_train_fused(const float* sigmas, const float* rgbs, const f
                                  float bg_b, int64_t* total_samples, float* opacity, float* depth, float* rgb,
                                  float* ws, float* dL_drgb, float* dL_dopacity, float* dL_dsigmas, float* dL_drgbs,
                                  float* loss_partials, mfnerf_stream_t stream) {
-    if (n_rays < 0 || n_samples < 0 || n_mean < 0 || (n_mean > 0 && n_mean < n_rays)) {
-        mfn_set_error("composite_train_fused: bad sizes"); return MFN_ERR_INVALID;
-    }
-    if (n_mean == 0) n_mean = n_rays;
-    if (n_rays == 0) return MFN_OK;
-    if (!rays_a || !target || !total_samples || !opacity || !depth || !rgb || !dL_drgb || !dL_dopacity ||
-        (n_samples > 0 && (!sigmas || !rgbs || !deltas || !ts || !ws || !dL_dsigmas || !dL_drgbs))) {
-        mfn_set_error("composite_train_fused: null pointer"); return MFN_ERR_INVALID;
-    }
-    hipLaunchKernelGGL(composite_fused_wave_kernel, dim3(blocks_for(n_rays, 4)), dim3(256), 0, stream, sigmas, rgbs,
-                       deltas, ts, rays_a, n_rays, T_threshold, target, n_mean, lambda_opacity, bg_r, bg_g, bg_b,
-                       total_samples, opacity, depth, rgb, ws, dL_drgb, dL_dopacity, dL_dsigmas, dL_drgbs,
-                       loss_partials);
-    return mfn_check_launch("composite_train_fused");
+    return composite_train_fused_launch<false>("composite_train_fused", sigmas, rgbs, deltas, ts, rays_a, n_rays,
+                                               n_samples, T_threshold, target, n_mean, lambda_opacity, bg_r, bg_g, bg_b,
+                                               total_samples, opacity, depth, rgb, ws, dL_drgb, dL_dopacity,
+                                               dL_dsigmas, dL_drgbs, loss_partials, stream);
+}
+
+int mfnerf_composite_train_fused_bg(const float* sigmas, const float* rgbs, const float* deltas, const float* ts,
+                                    const int64_t* rays_a, int64_t n_rays, int64_t n_samples, float T_threshold,
+                                    const float* target, int64_t n_mean, float lambda_opacity, const float* bg,
+                                    int64_t* total_samples, float* opacity, float* depth, float* rgb, float* ws,
+                                    float* dL_drgb, float* dL_dopacity, float* dL_dsigmas, float* dL_drgbs,
+                                    float* loss_partials, mfnerf_stream_t stream) {
+    if (!bg) { mfn_set_error("composite_train_fused_bg: null bg"); return MFN_ERR_INVALID; }
+    return composite_train_fused_launch<true>("composite_train_fused_bg", sigmas, rgbs, deltas, ts, rays_a, n_rays,
+                                              n_samples, T_threshold, target, n_mean, lambda_opacity, bg, BgUnused{},
+                                              BgUnused{}, total_samples, opacity, depth, rgb, ws, dL_drgb, dL_dopacity,
+                                              dL_dsigmas, dL_drgbs, loss_partials, stream);
 }
 
 int mfnerf_composite_test_fw(const float* sigmas, const float* rgbs, const float* deltas, const float* ts,
@@ -1038,13 +1109,16 @@ int mfnerf_distortion_loss_bw(const float* dL_dloss, const float* ws_incl, const
 int mfnerf_nerf_loss(const float* rgb, const float* opacity, const float* target, int64_t n_rays, int64_t n_mean,
                      float lambda_opacity, float bg_r, float bg_g, float bg_b, float* dL_drgb, float* dL_dopacity,
                      float* loss_sum, mfnerf_stream_t stream) {
-    if (n_rays < 0 || n_mean < 0 || (n_mean > 0 && n_mean < n_rays)) { mfn_set_error("nerf_loss: bad size"); return MFN_ERR_INVALID; }
-    if (n_mean == 0) n_mean = n_rays;
-    if (n_rays == 0) return MFN_OK;
-    if (!rgb || !opacity || !target || !dL_drgb || !dL_dopacity) { mfn_set_error("nerf_loss: null pointer"); return MFN_ERR_INVALID; }
-    hipLaunchKernelGGL(nerf_loss_kernel, dim3(blocks_for(n_rays, 256)), dim3(256), 0, stream, rgb, opacity, target,
-                       n_rays, n_mean, lambda_opacity, bg_r, bg_g, bg_b, dL_drgb, dL_dopacity, loss_sum);
-    return mfn_check_launch("nerf_loss");
+    return nerf_loss_launch<false>("nerf_loss", rgb, opacity, target, n_rays, n_mean, lambda_opacity, bg_r, bg_g, bg_b,
+                                   dL_drgb, dL_dopacity, loss_sum, stream);
+}
+
+int mfnerf_nerf_loss_bg(const float* rgb, const float* opacity, const float* target, int64_t n_rays, int64_t n_mean,
+                        float lambda_opacity, const float* bg, float* dL_drgb, float* dL_dopacity, float* loss_sum,
+                        mfnerf_stream_t stream) {
+    if (!bg) { mfn_set_error("nerf_loss_bg: null bg"); return MFN_ERR_INVALID; }
+    return nerf_loss_launch<true>("nerf_loss_bg", rgb, opacity, target, n_rays, n_mean, lambda_opacity, bg, BgUnused{},
+                                  BgUnused{}, dL_drgb, dL_dopacity, loss_sum, stream);
 }
 
 }  // extern "C"

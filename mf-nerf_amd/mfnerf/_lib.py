@@ -62,6 +62,8 @@ SIGNATURES = {
     "mfnerf_composite_train_bw": (_I, [_P] * 13 + [_I64, _I64, _F, _P, _P, _P]),
     "mfnerf_composite_train_fused": (_I, [_P, _P, _P, _P, _P, _I64, _I64, _F, _P, _I64, _F, _F, _F, _F]
                                      + [_P] * 10 + [_P]),
+    "mfnerf_composite_train_fused_bg": (_I, [_P, _P, _P, _P, _P, _I64, _I64, _F, _P, _I64, _F, _P]
+                                        + [_P] * 10 + [_P]),
     "mfnerf_composite_test_fw": (_I, [_P, _P, _P, _P, _P, _I64, _I, _F, _P, _P, _P, _P, _P]),
     "mfnerf_render_test_fused": (_I, [_P, _P, _I64, _P, _P, _P, _I, _F, _F, _I, _I, _I, _F, _F, _F,
                                       ctypes.POINTER(GridDesc), _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
@@ -70,6 +72,7 @@ SIGNATURES = {
     "mfnerf_distortion_loss_fw": (_I, [_P, _P, _P, _P, _I64, _I64, _P, _P, _P, _P]),
     "mfnerf_distortion_loss_bw": (_I, [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P]),
     "mfnerf_nerf_loss": (_I, [_P, _P, _P, _I64, _I64, _F, _F, _F, _F, _P, _P, _P, _P]),
+    "mfnerf_nerf_loss_bg": (_I, [_P, _P, _P, _I64, _I64, _F, _P, _P, _P, _P, _P]),
     "mfnerf_grid_encode_fw": (_I, [_P, _I64, _P, _F, _F, ctypes.POINTER(GridDesc), _P, _P, _P]),
     "mfnerf_grid_encode_fw_planar": (_I, [_P, _I64, _P, _F, _F, ctypes.POINTER(GridDesc), _P, _P, _I64, _P]),
     "mfnerf_grid_encode_bw_workspace": (_I64, [ctypes.POINTER(GridDesc)]),
@@ -116,6 +119,8 @@ SIGNATURES = {
                                      _P]),
     "mfnerf_sample_rays_prep_idx": (_I, [_P, _P, _P, _I64, _I64, _I64, _I, ctypes.c_uint64, _P, _P, _P, _P, _F, _P,
                                          _P, _P, _P, _P]),
+    "mfnerf_sample_rays_prep_bg": (_I, [_P, _P, _P, _I64, _I64, _I64, _I, ctypes.c_uint64, _P, _P, _P, _P, _F, _P,
+                                        _P, _P, _P, _P, _P]),
     "mfnerf_pose_grad": (_I, [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P]),
     "mfnerf_pose_step": (_I, [_P, _P, _P, _P, _P, _P, _P, _I64, _F, _F, _F, _F, _P, _P, _P, _P, _P]),
     "mfnerf_adam_step": (_I, [_P, _P, _P, _P, _P, _I64, _F, _F, _F, _F, _F, _I, _P, _P, _P, _I, _P]),

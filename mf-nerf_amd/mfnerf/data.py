@@ -302,13 +302,20 @@ class DeviceDataset:
 
     from_nsvf = from_dataset
 
-    def sample(self, out, img_idx=None, pix_idx=None, prep=None, poses=None):
+    def sample(self, out, img_idx=None, pix_idx=None, prep=None, poses=None, bg=None):
         """out (3, N, 3) f32 <- [rays_o | rays_d | rgb] of N random rays.  prep = (center, half_size,
         near, hits_t (N,2), noise (N)): also the march prologue (AABB hit, near clamp, noise) of the
         drawn rays, in the same launch (mfnerf_sample_rays_prep; with img_idx / pix_idx (N) i32, which
         receive the draws, mfnerf_sample_rays_prep_idx).  poses: a (n_img,3,4) f32 device buffer read
-        instead of self.poses (the refined poses of pose refinement)."""
+        instead of self.poses (the refined poses of pose refinement).  bg (3 f32, device; needs prep):
+        the batch's random background colour (--random_bg, rendering.py:153-161), drawn by the same
+        launch from (seed, draw counter) alone (mfnerf_sample_rays_prep_bg; img_idx / pix_idx optional)."""
         n = out.shape[1]
+        if bg is not None:
+            if prep is None:
+                raise ValueError("bg= is drawn with the march prologue: pass prep= too")
+            if bg.dtype != torch.float32 or bg.numel() != 3 or not bg.is_contiguous():
+                raise ValueError("bg= must be a contiguous float32 tensor of 3 values")
         if poses is None:
             poses = self.poses
         elif (poses.shape != self.poses.shape or poses.dtype != torch.float32 or not poses.is_contiguous()
@@ -316,6 +323,11 @@ class DeviceDataset:
             raise ValueError("poses= must be a contiguous float32 (n_img,3,4) tensor on the dataset's device")
         if prep is not None:
             center, half_size, near, hits_t, noise = prep
+            if bg is not None:
+                call("mfnerf_sample_rays_prep_bg", ptr(self.images), ptr(poses), ptr(self.directions), self.n_img,
+                     self.hw, n, self.same_image, self.seed, ptr(self.calls), ptr(out), ptr(center), ptr(half_size),
+                     float(near), ptr(hits_t), ptr(noise), ptr(img_idx), ptr(pix_idx), ptr(bg), stream())
+                return out
             if img_idx is not None or pix_idx is not None:
                 call("mfnerf_sample_rays_prep_idx", ptr(self.images), ptr(poses), ptr(self.directions), self.n_img,
                      self.hw, n, self.same_image, self.seed, ptr(self.calls), ptr(out), ptr(center), ptr(half_size),

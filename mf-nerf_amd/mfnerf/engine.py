@@ -81,6 +81,15 @@ class StepConfig:
     # no shard and no exchange.  Off: the same launches and buffers as without the option
     refine_poses: bool = False
     pose_lr: float = 1e-6
+    # --random_bg (opt.py:49, rendering.py:153-161): on a real scene (scale > 0.5) the prediction is
+    # blended over one random colour per training step -- every ray and every part of the step shares
+    # it -- instead of black, so dark objects are not explained away as transparent; the target is
+    # untouched.  The colour lives in the march buffer set of the batch it was drawn for (3 floats,
+    # mbuf[j].bg): with an attached dataset the batch's own draw launch writes it, so a replayed step
+    # reads the colour of the batch it trains on, not of the batch drawn ahead on the side stream.
+    # Synthetic scenes (scale <= 0.5) ignore the flag: white, bit for bit the step without it.  Off:
+    # the same launches and buffers as without the option
+    random_bg: bool = False
 
     def __post_init__(self):
         if self.refine_poses:
@@ -181,6 +190,8 @@ class TrainStep:
         self.cap_p = self.Np * c.max_samples          # sample capacity per part
         self.cap = N * c.max_samples
         self.parts = [self._part_buffers(q) for q in range(c.n_parts)]
+        # the fixed background (rendering.py:153-161): white on synthetic scenes, black on real ones
+        self._bg_const = torch.full((3,), 1.0 if c.scale <= 0.5 else 0.0, dtype=torch.float32, device=dev)
         self.mbuf = [self._march_buffers()]  # a second set is added by capture() (pipelined march)
         # the step's loss as partial sums: one per 4 rays of each part (written by the fused
         # compositing kernel) + 64 accumulated slots (unfused path: NeRFLoss atomics, distortion)
@@ -355,13 +366,27 @@ class TrainStep:
             m.part.append(t)
         if c.refine_poses and getattr(self, "dataset", None) is not None:
             self._pose_idx_buffers(m)
+        if self._random_bg():
+            m.bg = torch.zeros(3, **f32)  # the colour of the batch marched into this set
         return m
 
+    def _random_bg(self):
+        """random_bg in effect: the reference draws a colour only when exp_step_factor != 0
+        (rendering.py:153-161), here scale > 0.5."""
+        return self.cfg.random_bg and self.cfg.scale > 0.5
+
     def _use(self, mb):
-        """state.noise / state.counters / state.loss_sum of the step being run (inspection)."""
+        """state.noise / state.counters / state.loss_sum / state.bg of the step being run (inspection)."""
         st = self.state
         st.noise, st.counters, st.loss_parts, st.march = mb.noise, mb.counters, self.loss_parts, mb
         st.parts = self.parts
+        st.bg = mb.bg if self._random_bg() else self._bg_const
+
+    @property
+    def bg(self):
+        """The background colour (device 3-vector) the last step trained with: with random_bg on a real
+        scene the colour of that step's batch, else the constant white (synthetic) or black vector."""
+        return self.state.bg
 
     @property
     def loss_sum(self):
@@ -448,17 +473,19 @@ class TrainStep:
     # ---------------------------------------------------------------- the step
     def _draw(self, batch: Batch, mb):
         """The attached dataset's next batch into `batch`, with the march prologue (AABB + near clamp
-        + noise) of mb in the same launch."""
+        + noise) of mb in the same launch -- and, random_bg, the batch's background colour into mb.bg."""
         prep = (self.center, self.half_size, NEAR_DISTANCE, mb.hits, mb.noise)
+        kw = {"bg": mb.bg} if self._random_bg() else {}
         if self.cfg.refine_poses:
             self.dataset.sample(batch.buf, prep=prep, img_idx=mb.img_idx, pix_idx=mb.pix_idx,
-                                poses=self.pose_buf[self.mbuf.index(mb)])
+                                poses=self.pose_buf[self.mbuf.index(mb)], **kw)
         else:
-            self.dataset.sample(batch.buf, prep=prep)
+            self.dataset.sample(batch.buf, prep=prep, **kw)
 
-    def _march(self, batch: Batch, mb, mark, prepped=False, noise=None):
-        """AABB + near clamp + noise for the whole batch (unless _draw did it), then one ray march per
-        part into mb."""
+    def _march(self, batch: Batch, mb, mark, prepped=False, noise=None, bg=None):
+        """AABB + near clamp + noise (and, random_bg, the background colour: from the step's generator
+        after the noise, or the given bg) for the whole batch (unless _draw did it), then one ray march
+        per part into mb."""
         c, s = self.cfg, stream()
         N, Np = c.n_rays, self.Np
         if not prepped:
@@ -471,6 +498,11 @@ class TrainStep:
                 torch.rand(N, generator=self.gen, device=self.dev, out=mb.noise)
             else:  # a given perturbation (parity tests driving the reference with the same draws)
                 mb.noise.copy_(noise)
+            if self._random_bg():  # rendering.py:160: one colour for the whole batch
+                if bg is None:
+                    torch.rand(3, generator=self.gen, device=self.dev, out=mb.bg)
+                else:
+                    mb.bg.copy_(torch.as_tensor(bg, dtype=torch.float32).reshape(3))
         mark("prep")
         for q, t in enumerate(mb.part):
             r = slice(q * Np, (q + 1) * Np)
@@ -506,21 +538,24 @@ class TrainStep:
         call("mfnerf_field_fw", ptr(t.feat), cap, ptr(m.dirs), cap, ptr(m.counter), ptr(self.packed), c.rgb_width, 0,
              ptr(t.sigma), ptr(t.rgb_s), s)
         mark("field_fw")
+        # the background: three scalars, or (random_bg) the 3 floats the batch's draw left in mb.bg,
+        # read by the _bg forms of the two loss-carrying kernels (every part reads the one colour)
         bg = 1.0 if c.scale <= 0.5 else 0.0
+        sfx, bg_args = ("_bg", (ptr(mb.bg),)) if self._random_bg() else ("", (bg, bg, bg))
         target = ptr(batch.rgb[q * Np:(q + 1) * Np])
         if c.lambda_distortion <= 0:
             # composite fw -> bg blend + NeRFLoss -> composite bw in one wave-per-ray launch
             args = (ptr(t.sigma), ptr(t.rgb_s), ptr(m.deltas), ptr(m.ts), ptr(m.rays_a), Np, cap, c.T_threshold,
-                    target, c.n_rays, c.lambda_opacity, bg, bg, bg, ptr(t.total), ptr(t.opacity), ptr(t.depth),
+                    target, c.n_rays, c.lambda_opacity, *bg_args, ptr(t.total), ptr(t.opacity), ptr(t.depth),
                     ptr(t.rgb), ptr(t.ws), ptr(t.dL_drgb), ptr(t.dL_dop), ptr(t.dsig), ptr(t.drgb_s),
                     ptr(self.loss_parts[q * self._nb_part:]))
-            call("mfnerf_composite_train_fused", *args, s)
+            call("mfnerf_composite_train_fused" + sfx, *args, s)
             mark("composite")
         else:
             call("mfnerf_composite_train_fw", ptr(t.sigma), ptr(t.rgb_s), ptr(m.deltas), ptr(m.ts), ptr(m.rays_a),
                  Np, cap, c.T_threshold, ptr(t.total), ptr(t.opacity), ptr(t.depth), ptr(t.rgb), ptr(t.ws), s)
-            call("mfnerf_nerf_loss", ptr(t.rgb), ptr(t.opacity), target, Np, c.n_rays, c.lambda_opacity, bg, bg, bg,
-                 ptr(t.dL_drgb), ptr(t.dL_dop), ptr(self._loss_acc), s)
+            call("mfnerf_nerf_loss" + sfx, ptr(t.rgb), ptr(t.opacity), target, Np, c.n_rays, c.lambda_opacity,
+                 *bg_args, ptr(t.dL_drgb), ptr(t.dL_dop), ptr(self._loss_acc), s)
             # losses.py:6-37 + 55-58
             call("mfnerf_distortion_loss_fw", ptr(t.ws), ptr(m.deltas), ptr(m.ts), ptr(m.rays_a), Np, cap,
                  ptr(t.dist_loss), ptr(t.ws_incl), ptr(t.wts_incl), s)
@@ -781,13 +816,26 @@ class TrainStep:
             else:
                 self._update()
 
-    def run(self, batch: Batch = None, mark=None, exchange=None, optimize=True, noise=None):
+    def _check_bg(self, *given):
+        """bg= / next_bg= are for a step that passes its batches with random_bg on (ignored on a
+        synthetic scene, like the flag): an attached dataset's draw writes the colour itself."""
+        if all(b is None for b in given):
+            return
+        if not self.cfg.random_bg:
+            raise ValueError("bg= needs StepConfig(random_bg=True)")
+        if self.dataset is not None:
+            raise ValueError("bg= is for batches the caller passes: the attached dataset's draw writes the colour")
+
+    def run(self, batch: Batch = None, mark=None, exchange=None, optimize=True, noise=None, bg=None):
         """One training step, eagerly on the current stream, parts in sequence, march buffer set 0.
         mark(name) is called after each stage (bench timing); exchange(grads) runs between backward
         and Adam (the data-parallel all-reduce).  batch=None: drawn from the attached dataset.
         optimize=False stops after the backward and leaves the step's gradient in self.grads (no
-        Adam step, no repack; for inspection)."""
+        Adam step, no repack; for inspection).  random_bg: the step's background colour comes with
+        the dataset's draw; for a passed batch it is bg (3 values) or, bg=None, three draws from the
+        step's generator after the noise."""
         mark = mark or (lambda name: None)
+        self._check_bg(bg)
         if self.cfg.refine_poses:
             self._check_refine(exchange)
             if batch is not None:
@@ -801,7 +849,7 @@ class TrainStep:
         self._use(mb)
         self.last_batch = batch
         self._primed = False  # a pipelined replay() must march its own batch next
-        self._march(batch, mb, mark, prepped=prepped, noise=noise)
+        self._march(batch, mb, mark, prepped=prepped, noise=noise, bg=bg)
         dp = self.shard is not None or exchange is not None
         for q in range(self.n_parts):
             self._chain(batch, mb, q, mark)
@@ -845,7 +893,12 @@ class TrainStep:
         way.  The per-stage graphs (march[j], chain[j][q], grid_bw[j][q], finish, update / adam +
         pack) serve several parts and the steps whose scatter is timed by events (bench).
         host_noise: the march perturbation is copied from a buffer replay(noise=...) fills instead of
-        drawn from the step's generator (parity tests driving several processes with one draw).
+        drawn from the step's generator (parity tests driving several processes with one draw); with
+        random_bg and no attached dataset the background colour is staged the same way
+        (replay(bg=, next_bg=)).  random_bg: the colour is part of the march graph (the dataset's draw
+        launch, or the generator / staged copy), written into the march buffer set the batch goes
+        into, so the step graph of set j reads the colour of the batch it trains on while the next
+        batch's colour waits in set 1-j.
         Call after at least one eager step (lazy library init happens outside capture)."""
         N = self.cfg.n_rays
         self._check_refine()
@@ -857,6 +910,8 @@ class TrainStep:
         self._static = [_packed_batch(torch.zeros(3, N, 3, device=self.dev)) for _ in range(2)]
         self._host_noise = bool(host_noise)
         self._static_noise = [torch.zeros(N, device=self.dev) for _ in range(2)] if host_noise else None
+        host_bg = host_noise and self._random_bg() and self.dataset is None
+        self._static_bg = [torch.zeros(3, device=self.dev) for _ in range(2)] if host_bg else None
         torch.cuda.synchronize()
         pool = torch.cuda.graph_pool_handle()
         nomark = lambda _n: None  # noqa: E731
@@ -874,7 +929,8 @@ class TrainStep:
             if self.dataset is not None:
                 self._draw(self._static[j], self.mbuf[j])
             self._march(self._static[j], self.mbuf[j], nomark, prepped=self.dataset is not None,
-                        noise=self._static_noise[j] if host_noise else None)
+                        noise=self._static_noise[j] if host_noise else None,
+                        bg=self._static_bg[j] if host_bg else None)
 
         self.graphs = {
             "march": [cap(lambda j=j: march(j), rng=True) for j in range(2)],
@@ -1008,8 +1064,9 @@ class TrainStep:
             for d, s_ in zip((dst.rays_o, dst.rays_d, dst.rgb), (batch.rays_o, batch.rays_d, batch.rgb)):
                 d.copy_(s_)
 
-    def _march_on_side(self, j, batch, after, gated=False, noise=None):
-        """Copy batch (and, captured with host_noise, its perturbation) into static set j and march
+    def _march_on_side(self, j, batch, after, gated=False, noise=None, bg=None):
+        """Copy batch (and, captured with host_noise, its perturbation and, random_bg without a dataset,
+        its background colour) into static set j and march
         it on the side stream once `after` (an event on the main stream) has passed: set j's buffers
         were last read two steps back.  gated: the march graph first waits (a polling wave, at most
         GATE_TIMEOUT_US) for the step graph's gate signal (placement only)."""
@@ -1021,11 +1078,15 @@ class TrainStep:
                 if noise is None:
                     raise ValueError("captured with host_noise: pass noise= / next_noise= to replay()")
                 self._static_noise[j].copy_(noise)
+            if self._static_bg is not None:
+                if bg is None:
+                    raise ValueError("captured with host_noise and random_bg: pass bg= / next_bg= to replay()")
+                self._static_bg[j].copy_(torch.as_tensor(bg, dtype=torch.float32).reshape(3))
             self.graphs["march_gated" if gated else "march"][j].replay()
             self._ev_march[j].record(self._side)
 
     def replay(self, batch: Batch = None, exchange=None, grid_bw_events=None, next_batch=None, prefetch=None,
-               noise=None, next_noise=None):
+               noise=None, next_noise=None, bg=None, next_bg=None):
         """One training step from the captured graphs (the kernels of run()).  With next_batch (or,
         with an attached dataset, prefetch=True, its default), the next step's march is issued on
         the side stream to overlap this step; the next replay() must then be called with that batch
@@ -1034,10 +1095,12 @@ class TrainStep:
         Data parallel: sharded (shard_optimizer) or exchange=dp.allreduce_mean_.
         grid_bw_events: optional (start, [end per part]) timing events -- start before part 0's
         grid_bw, end after each part's grid_bw (that step runs the per-stage graphs).
-        noise / next_noise: the perturbations of batch / next_batch (capture(host_noise=True))."""
+        noise / next_noise: the perturbations of batch / next_batch (capture(host_noise=True));
+        bg / next_bg: their background colours (random_bg, capture(host_noise=True), no dataset)."""
         from . import dp
         g, j, P = self.graphs, self._parity, self.n_parts
         self._check_refine(exchange)
+        self._check_bg(bg, next_bg)
         dp_mode = self.shard is not None or exchange is not None
         if self.dataset is not None:
             batch = None
@@ -1050,7 +1113,7 @@ class TrainStep:
         main = torch.cuda.current_stream()
         self._ev_start.record(main)
         if not self._primed:
-            self._march_on_side(j, batch, self._ev_start, noise=noise)
+            self._march_on_side(j, batch, self._ev_start, noise=noise, bg=bg)
         one_graph = P == 1 and grid_bw_events is None and prefetch and g.get("march_gated") is not None
         if one_graph and (dp_mode or g.get("step") is not None):
             # set 1-j was last read by the previous step, all of which precedes _ev_start
@@ -1060,16 +1123,16 @@ class TrainStep:
             self.adam_step += 1
             if not dp_mode:  # one graph for the step; the next march starts at its gate signal
                 g["step"][j].replay()
-                self._march_on_side(1 - j, next_batch, self._ev_start, gated=True, noise=next_noise)
+                self._march_on_side(1 - j, next_batch, self._ev_start, gated=True, noise=next_noise, bg=next_bg)
             elif g.get("dp_step") is not None and (self.shard is not None or exchange is dp.allreduce_mean_):
                 # the whole data-parallel step, collectives included, as one graph (direct RCCL)
                 g["dp_step"][j].replay()
-                self._march_on_side(1 - j, next_batch, self._ev_start, gated=True, noise=next_noise)
+                self._march_on_side(1 - j, next_batch, self._ev_start, gated=True, noise=next_noise, bg=next_bg)
                 self._stale_pack = True  # the next step's graph starts with the repack
             else:
                 # [repack] chain, scatter, float gradient, flag -> collective -> Adam -> (all-gather)
                 g["dp_pre"][j].replay()
-                self._march_on_side(1 - j, next_batch, self._ev_start, gated=True, noise=next_noise)
+                self._march_on_side(1 - j, next_batch, self._ev_start, gated=True, noise=next_noise, bg=next_bg)
                 if self.shard is not None:
                     dp.reduce_scatter_mean_(self.g_shard, self.grads)
                     g["dp_post"].replay()
@@ -1096,7 +1159,7 @@ class TrainStep:
                 if q == P - 1 and prefetch:
                     # set 1-j was last read by the previous step, which this chain follows; waiting
                     # for the last chain puts the march under the grid_bw scatters, not the chains
-                    self._march_on_side(1 - j, next_batch, self._ev_chain[q], noise=next_noise)
+                    self._march_on_side(1 - j, next_batch, self._ev_chain[q], noise=next_noise, bg=next_bg)
                 if fuse_tail and grid_bw_events is None:
                     # P == 1: scatter + convert/Adam + repack as one graph (no event needed between)
                     self.adam_step += 1

@@ -15,6 +15,11 @@ the step.
   unpinned: the parity fixtures come from an fp32 reference and assert zero skips).  All of it on the
   device (mfnerf_field_bw's non-finite flag and device scale, the optimizer pass's last workgroup
   running GradScaler.update(); mfnerf_amp_state) -- no host synchronisation;
+* random background -- --random_bg (opt.py:49, rendering.py:153-161, train.py:98-99): on a real scene
+  (scale > 0.5) every training step blends its prediction over one random colour, drawn on the device
+  by the launch that draws the step's batch (so a replayed step reads the colour of the batch it
+  trains on, not of the batch drawn ahead); the draw is a counter hash of (dataset seed, draw count),
+  not torch.rand's stream.  Synthetic scenes ignore the flag; test-time rendering keeps its black;
 * metrics -- train loss / PSNR / rm_s (train.py:178-189), read back only every `log_every` steps;
   test PSNR with the test-time renderer (evaluate, train.py:197-206) and test PSNR + SSIM
   (validate, train.py:198-237: mfnerf.metrics, fp64 on the device, one read-back per test set);
@@ -73,8 +78,6 @@ def psnr(pred, gt):
 
 class Trainer:
     def __init__(self, hp: HParams, train, device="cuda", rank=0, world=1, graphs=True):
-        if hp.random_bg:
-            raise NotImplementedError("the fused step trains with a fixed background (random_bg off)")
         if hp.rgb_layers != 2:
             raise NotImplementedError("the fused field head implements rgb_layers=2")
         if hp.optimize_ext and world > 1:
@@ -84,7 +87,7 @@ class Trainer:
         cfg = engine.StepConfig(n_rays=hp.batch_size, scale=hp.scale, L=hp.L, F=hp.F, log2_T=hp.T, N_min=hp.N_min,
                                 N_max=hp.N_max, grid=hp.grid, N_tables=hp.N_tables, rgb_width=hp.rgb_channels,
                                 lr=hp.lr, lambda_distortion=hp.distortion_loss_w, refine_poses=hp.optimize_ext,
-                                pose_lr=hp.pose_lr)
+                                pose_lr=hp.pose_lr, random_bg=hp.random_bg)
         self.step = engine.TrainStep(cfg, device=device, seed=hp.seed)
         if world > 1:
             self.step.shard_optimizer(rank, world)
@@ -146,11 +149,13 @@ class Trainer:
 
     @torch.no_grad()
     def train_metrics(self):
-        """train.py:178-189 for the last step: loss, PSNR of the batch, rm_s."""
+        """train.py:178-189 for the last step: loss, PSNR of the batch, rm_s.  The prediction is blended
+        over the background the step trained with (st.bg: with random_bg the batch's own colour), so
+        the PSNR is that of the loss the step minimised."""
         st = self.step
         b = st.last_batch
-        bg = 1.0 if st.cfg.scale <= 0.5 else 0.0
-        preds = [t.rgb + bg * (1 - t.opacity)[:, None] for t in st.parts]
+        bg = st.bg
+        preds = [t.rgb + bg[None] * (1 - t.opacity)[:, None] for t in st.parts]
         pred = torch.cat(preds)
         return {"step": self.global_step, "loss": float(st.loss_sum), "psnr": psnr(pred, b.rgb),
                 "rm_s": float(st.live_samples()) / st.cfg.n_rays,
