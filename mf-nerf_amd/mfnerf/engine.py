@@ -22,6 +22,7 @@ Multi-GPU: run/replay(exchange=dp.allreduce_mean_) all-reduces `grads` between b
 import ctypes
 import math
 from dataclasses import dataclass
+from typing import Optional
 
 import numpy as np
 import torch
@@ -35,6 +36,13 @@ MAX_SAMPLES = 1024
 GATE_TIMEOUT_US = 2000  # a gated march starts anyway after this long (gate.hip)
 NEAR_DISTANCE = 0.01
 SQRT3 = 3 ** 0.5
+DENSITY_THRESHOLD = 0.01 * MAX_SAMPLES / SQRT3  # NGP.update_density_grid's threshold (train.py:165-168)
+ADAM_BETAS = (0.9, 0.999)
+POSE_ADAM_EPS = 1e-8
+# synthetic scenes (scale <= 0.5) march with uniform steps over a white background; real scenes with
+# exponentially growing steps over black, or a random colour (rendering.py:121-161)
+EXP_STEP_FACTOR = 1 / 256
+BG_SYNTHETIC, BG_REAL = 1.0, 0.0
 
 
 @dataclass
@@ -101,6 +109,7 @@ class Batch:
     rays_o: torch.Tensor
     rays_d: torch.Tensor
     rgb: torch.Tensor
+    buf: Optional[torch.Tensor] = None  # the (3, N, 3) buffer the three are views into, if packed
 
 
 class _State:
@@ -112,9 +121,10 @@ class _State:
 
 def _packed_batch(buf):
     """Batch whose tensors are views into one (3, N, 3) buffer (rays_o, rays_d, rgb)."""
-    b = Batch(buf[0], buf[1], buf[2])
-    b.buf = buf
-    return b
+    return Batch(buf[0], buf[1], buf[2], buf)
+
+
+_nomark = lambda _name: None  # noqa: E731  (the mark= of a step nobody times)
 
 
 def init_params(c: StepConfig, n_params, n_alloc, seed):
@@ -157,6 +167,7 @@ class TrainStep:
         self.n_alloc = -(-self.n_params // 16384) * 16384
         s32 = np.float32(c.scale)
         self.x_min, self.x_range = float(-s32), float(np.float32(s32) - np.float32(-s32))
+        self.exp_step_factor, self.bg_value = (EXP_STEP_FACTOR, BG_REAL) if c.scale > 0.5 else (0.0, BG_SYNTHETIC)
 
         dev = self.dev
         self.params = init_params(c, self.n_params, self.n_alloc, seed).to(dev)
@@ -164,7 +175,7 @@ class TrainStep:
         self.m = torch.zeros(self.n_alloc, device=dev)
         self.v = torch.zeros(self.n_alloc, device=dev)
         self.p16 = self.params.half()
-        self.shard = None  # (rank, lo, hi) once shard_optimizer() is on
+        self.shard = self.g_shard = None  # shard_optimizer(): (rank, lo, hi), this rank's slice of grads
         # mfnerf_amp_state: [non-finite flag, skipped steps, scale, growth tracker, growth interval,
         # growth factor, backoff factor, ticket] (include/mfnerf.h)
         self.finite_status = torch.zeros(8, dtype=torch.int32, device=dev)
@@ -189,9 +200,14 @@ class TrainStep:
         self.Np = N // c.n_parts                      # rays per part
         self.cap_p = self.Np * c.max_samples          # sample capacity per part
         self.cap = N * c.max_samples
+        self._bin_supported = (c.n_parts == 1 and c.fixed_point_grid and c.binned_grid and
+                               load().mfnerf_grid_encode_bw_binned_workspace(self.desc, self._bin_slots()) >= 0)
+        self._store_fold_v = self._store_fold()
+        self._fused_args = None  # the last mfnerf_adam_fused handed to a launch, kept alive for the graphs
         self.parts = [self._part_buffers(q) for q in range(c.n_parts)]
-        # the fixed background (rendering.py:153-161): white on synthetic scenes, black on real ones
-        self._bg_const = torch.full((3,), 1.0 if c.scale <= 0.5 else 0.0, dtype=torch.float32, device=dev)
+        self._bg_const = torch.full((3,), self.bg_value, dtype=torch.float32, device=dev)
+        # attach_dataset: the dataset, the batch drawn from it (and, refine_poses only, _pose_buffers)
+        self.dataset = self._sampled = None
         self.mbuf = [self._march_buffers()]  # a second set is added by capture() (pipelined march)
         # the step's loss as partial sums: one per 4 rays of each part (written by the fused
         # compositing kernel) + 64 accumulated slots (unfused path: NeRFLoss atomics, distortion)
@@ -206,9 +222,16 @@ class TrainStep:
         # static fp16 backward scale: per-sample grads are O(1/n_rays); 2^(floor(log2 N)-2) keeps them
         # normal.  With the dynamic scale (default) field_bw reads amp.scale on the device instead.
         self.grad_scale = float(2.0 ** max(0, int(math.floor(math.log2(N))) - 2))
-        self._primed = False
+        self.last_batch = None    # the batch of the last step (run: as passed or drawn; replay: the static set)
         self._stale_pack = False  # a one-graph data-parallel replay left `packed` one update behind
-        self.dataset = None
+        self._occ = None          # the occupancy refresh's scratch and graphs (_occ_buffers)
+        # what capture() makes: static inputs per march buffer set, the device gate of the gated march
+        # ({signals, waits, -, timeouts}; None: the captured step is not gated), streams and events
+        self._static, self._static_noise, self._static_bg, self._host_noise = [], None, None, False
+        self._gate, self._gate_opened, self._side, self._part_streams = None, 0, None, []
+        self._ev_start, self._ev_march, self._ev_chain, self._ev_part = None, [], [], []
+        self._parity = 0      # the march buffer set of the next replay
+        self._primed = False  # ... whose batch is already marched (by the previous replay)
 
     def reset_loss_scale(self, scale=None):
         """(Re)initialise the device GradScaler state (mfnerf_amp_state) from the config."""
@@ -286,7 +309,7 @@ class TrainStep:
         idle (capture() and a checkpoint load do)."""
         for buf in self.pose_buf:
             call("mfnerf_pose_step", ptr(self.dR), ptr(self.dT), None, None, None, None, ptr(self.dataset.poses),
-                 self.dataset.n_img, 0.0, 0.9, 0.999, 1e-8, None, None, None, ptr(buf), stream())
+                 self.dataset.n_img, 0.0, *ADAM_BETAS, POSE_ADAM_EPS, None, None, None, ptr(buf), stream())
 
     def _pose_update(self, mb):
         """After the ray gradients of the step on mb: the per-image reduction, the pose Adam step (skipped
@@ -296,8 +319,8 @@ class TrainStep:
              ptr(ds.poses), ptr(ds.directions), ptr(self.dR), self.cfg.n_rays, ds.n_img, ds.hw,
              ptr(self.pose_grad[0]), ptr(self.pose_grad[1]), self._amp_ptr(), stream())
         call("mfnerf_pose_step", ptr(self.dR), ptr(self.dT), ptr(self.pose_m), ptr(self.pose_v),
-             ptr(self.pose_grad[0]), ptr(self.pose_grad[1]), ptr(ds.poses), ds.n_img, float(self.cfg.pose_lr), 0.9,
-             0.999, 1e-8, ptr(self.pose_step_dev), ptr(self.pose_lr_dev), self._amp_ptr(),
+             ptr(self.pose_grad[0]), ptr(self.pose_grad[1]), ptr(ds.poses), ds.n_img, float(self.cfg.pose_lr),
+             *ADAM_BETAS, POSE_ADAM_EPS, ptr(self.pose_step_dev), ptr(self.pose_lr_dev), self._amp_ptr(),
              ptr(self.pose_buf[self.mbuf.index(mb)]), stream())
 
     # ---------------------------------------------------------------- buffers
@@ -332,10 +355,8 @@ class TrainStep:
             t.ddirs = torch.empty(cap, 3, **f32)
             t.dL_drays_o = torch.zeros(Np, 3, **f32)
             t.dL_drays_d = torch.zeros(Np, 3, **f32)
-        if self._binned():
-            nb = load().mfnerf_grid_encode_bw_binned_workspace(self.desc, self._bin_slots())
-        else:
-            nb = load().mfnerf_grid_encode_bw_workspace(self.desc)
+        nb = (load().mfnerf_grid_encode_bw_binned_workspace(self.desc, self._bin_slots()) if self._binned()
+              else load().mfnerf_grid_encode_bw_workspace(self.desc))
         t.grid_ws = torch.zeros(max(16, nb) // 4, **f32)
         # parts > 0 accumulate their MLP weight grads privately (field_bw's slab sum is a plain +=)
         t.mlp_grad = self.grads[:self.off_table] if q == 0 else torch.zeros(self.off_table, **f32)
@@ -364,7 +385,7 @@ class TrainStep:
             ws_bytes = load().mfnerf_raymarching_train_workspace(self.Np, c.max_samples)
             t.march_ws = torch.empty(max(16, ws_bytes), dtype=torch.uint8, device=dev)
             m.part.append(t)
-        if c.refine_poses and getattr(self, "dataset", None) is not None:
+        if c.refine_poses and self.dataset is not None:
             self._pose_idx_buffers(m)
         if self._random_bg():
             m.bg = torch.zeros(3, **f32)  # the colour of the batch marched into this set
@@ -428,8 +449,8 @@ class TrainStep:
     def set_occupancy(self, density_grid):
         """Install a (C, G^3) density grid and pack it with the reference's threshold."""
         self.density_grid.copy_(density_grid.to(self.dev))
-        thr = 0.01 * MAX_SAMPLES / SQRT3
-        call("mfnerf_packbits", ptr(self.density_grid), self.bitfield.numel(), thr, None, ptr(self.bitfield), stream())
+        call("mfnerf_packbits", ptr(self.density_grid), self.bitfield.numel(), DENSITY_THRESHOLD, None,
+             ptr(self.bitfield), stream())
 
     def _pack(self):
         """MFMA weight blob from the fp16 compute copy (the fp16 values packing the fp32 master
@@ -467,7 +488,7 @@ class TrainStep:
         # this rank's slice of the gradient, reduced in place (RCCL in-place reduce-scatter: no
         # second gradient-sized buffer, and a one-rank group's "reduction" is no copy)
         self.g_shard = self.grads[lo:hi]
-        self._store_fold_v = None  # (re-derived for the sharded step)
+        self._store_fold_v = self._store_fold()
         self.graphs = None  # re-capture with the sharded update
 
     # ---------------------------------------------------------------- the step
@@ -477,10 +498,8 @@ class TrainStep:
         prep = (self.center, self.half_size, NEAR_DISTANCE, mb.hits, mb.noise)
         kw = {"bg": mb.bg} if self._random_bg() else {}
         if self.cfg.refine_poses:
-            self.dataset.sample(batch.buf, prep=prep, img_idx=mb.img_idx, pix_idx=mb.pix_idx,
-                                poses=self.pose_buf[self.mbuf.index(mb)], **kw)
-        else:
-            self.dataset.sample(batch.buf, prep=prep, **kw)
+            kw.update(img_idx=mb.img_idx, pix_idx=mb.pix_idx, poses=self.pose_buf[self.mbuf.index(mb)])
+        self.dataset.sample(batch.buf, prep=prep, **kw)
 
     def _march(self, batch: Batch, mb, mark, prepped=False, noise=None, bg=None):
         """AABB + near clamp + noise (and, random_bg, the background colour: from the step's generator
@@ -507,14 +526,18 @@ class TrainStep:
         for q, t in enumerate(mb.part):
             r = slice(q * Np, (q + 1) * Np)
             call("mfnerf_raymarching_train", ptr(batch.rays_o[r]), ptr(batch.rays_d[r]), ptr(mb.hits_t[r]), 2,
-                 ptr(self.bitfield), self.cascades, float(c.scale), 0.0 if c.scale <= 0.5 else 1 / 256,
-                 ptr(mb.noise[r]), self.G, c.max_samples, Np, self.cap_p, ptr(t.rays_a), ptr(t.xyzs), ptr(t.dirs),
-                 ptr(t.deltas), ptr(t.ts), ptr(t.counter), ptr(t.march_ws), s)
+                 ptr(self.bitfield), self.cascades, float(c.scale), self.exp_step_factor, ptr(mb.noise[r]), self.G,
+                 c.max_samples, Np, self.cap_p, ptr(t.rays_a), ptr(t.xyzs), ptr(t.dirs), ptr(t.deltas), ptr(t.ts),
+                 ptr(t.counter), ptr(t.march_ws), s)
         # running total of marched samples (rm_s without a read on the step's critical path: in the
-        # graphs this runs on the march's side stream)
-        # one kernel on the side chain for one part (a slice + reduce + add otherwise)
+        # graphs this runs on the march's side stream): one kernel for one part, else slice + reduce + add
         self.samples_marched.add_(mb.counters[0, 0] if self.n_parts == 1 else mb.counters[:, 0].sum())
         mark("march")
+
+    def _enc_args(self, mb, q):
+        """The encoding's forward and every scatter start with: part q's samples in mb, their count, box, grid."""
+        m = mb.part[q]
+        return ptr(m.xyzs), self.cap_p, ptr(m.counter), self.x_min, self.x_range, self.desc
 
     def _chain(self, batch: Batch, mb, q, mark):
         """Part q: encode -> field -> composite -> loss -> composite bw -> field bw (no grid bw).
@@ -522,7 +545,7 @@ class TrainStep:
         c, s = self.cfg, stream()
         t, m = self.parts[q], mb.part[q]
         Np, cap = self.Np, self.cap_p
-        store_fold = q == 0 and self._store_fold()
+        store_fold = q == 0 and self._store_fold_v
         if q == 0:
             if self.shard is not None and not store_fold:
                 # unsharded: the previous Adam pass left it zero; sharded, the binned scatter
@@ -532,28 +555,27 @@ class TrainStep:
                 self._loss_acc.zero_()
         else:
             t.mlp_grad.zero_()
-        call("mfnerf_grid_encode_fw_planar", ptr(m.xyzs), cap, ptr(m.counter), self.x_min, self.x_range, self.desc,
-             ptr(self.p16[self.off_table:]), ptr(t.feat), cap, s)
+        call("mfnerf_grid_encode_fw_planar", *self._enc_args(mb, q), ptr(self.p16[self.off_table:]), ptr(t.feat),
+             cap, s)
         mark("grid_fw")
         call("mfnerf_field_fw", ptr(t.feat), cap, ptr(m.dirs), cap, ptr(m.counter), ptr(self.packed), c.rgb_width, 0,
              ptr(t.sigma), ptr(t.rgb_s), s)
         mark("field_fw")
         # the background: three scalars, or (random_bg) the 3 floats the batch's draw left in mb.bg,
         # read by the _bg forms of the two loss-carrying kernels (every part reads the one colour)
-        bg = 1.0 if c.scale <= 0.5 else 0.0
+        bg = self.bg_value
         sfx, bg_args = ("_bg", (ptr(mb.bg),)) if self._random_bg() else ("", (bg, bg, bg))
         target = ptr(batch.rgb[q * Np:(q + 1) * Np])
+        comp_in = (ptr(t.sigma), ptr(t.rgb_s), ptr(m.deltas), ptr(m.ts), ptr(m.rays_a), Np, cap, c.T_threshold)
+        comp_out = (ptr(t.total), ptr(t.opacity), ptr(t.depth), ptr(t.rgb), ptr(t.ws))
         if c.lambda_distortion <= 0:
             # composite fw -> bg blend + NeRFLoss -> composite bw in one wave-per-ray launch
-            args = (ptr(t.sigma), ptr(t.rgb_s), ptr(m.deltas), ptr(m.ts), ptr(m.rays_a), Np, cap, c.T_threshold,
-                    target, c.n_rays, c.lambda_opacity, *bg_args, ptr(t.total), ptr(t.opacity), ptr(t.depth),
-                    ptr(t.rgb), ptr(t.ws), ptr(t.dL_drgb), ptr(t.dL_dop), ptr(t.dsig), ptr(t.drgb_s),
-                    ptr(self.loss_parts[q * self._nb_part:]))
-            call("mfnerf_composite_train_fused" + sfx, *args, s)
+            call("mfnerf_composite_train_fused" + sfx, *comp_in, target, c.n_rays, c.lambda_opacity, *bg_args,
+                 *comp_out, ptr(t.dL_drgb), ptr(t.dL_dop), ptr(t.dsig), ptr(t.drgb_s),
+                 ptr(self.loss_parts[q * self._nb_part:]), s)
             mark("composite")
         else:
-            call("mfnerf_composite_train_fw", ptr(t.sigma), ptr(t.rgb_s), ptr(m.deltas), ptr(m.ts), ptr(m.rays_a),
-                 Np, cap, c.T_threshold, ptr(t.total), ptr(t.opacity), ptr(t.depth), ptr(t.rgb), ptr(t.ws), s)
+            call("mfnerf_composite_train_fw", *comp_in, *comp_out, s)
             call("mfnerf_nerf_loss" + sfx, ptr(t.rgb), ptr(t.opacity), target, Np, c.n_rays, c.lambda_opacity,
                  *bg_args, ptr(t.dL_drgb), ptr(t.dL_dop), ptr(self._loss_acc), s)
             # losses.py:6-37 + 55-58
@@ -569,11 +591,8 @@ class TrainStep:
             mark("composite_bw")
         bw_args = (ptr(t.feat), cap, ptr(m.dirs), cap, ptr(m.counter), ptr(self.packed), c.rgb_width,
                    ptr(t.dsig), ptr(t.drgb_s), 0.0 if c.dynamic_loss_scale else self.grad_scale, ptr(t.dfeat),
-                   None if store_fold else ptr(t.mlp_grad),
-                   None if store_fold else ptr(t.mlp_grad[self.off_rgb:]),
-                   ptr(t.field_ws),
-                   self._amp_ptr(),
-                   ptr(self._level_l1) if self._fixed() else None)
+                   None if store_fold else ptr(t.mlp_grad), None if store_fold else ptr(t.mlp_grad[self.off_rgb:]),
+                   ptr(t.field_ws), self._amp_ptr(), ptr(self._level_l1) if self._fixed() else None)
         if c.ray_grads:
             # the same backward plus dL/ddirs, then dL/dxyz through the encoding summed per ray
             # (the table is the fp16 copy the forward gathered from: Adam comes later in the step)
@@ -601,10 +620,6 @@ class TrainStep:
         """The fixed-point table gradient by table partitions (one part only, like _fixed), for the
         layouts the partitioned scatter supports; any other layout the reference accepts (opt.py:78,
         e.g. --T 21) keeps the request-shaped fixed-point atomic scatter."""
-        if not (self.cfg.n_parts == 1 and self.cfg.fixed_point_grid and self.cfg.binned_grid):
-            return False
-        if getattr(self, "_bin_supported", None) is None:
-            self._bin_supported = load().mfnerf_grid_encode_bw_binned_workspace(self.desc, self._bin_slots()) >= 0
         return self._bin_supported
 
     def _bin_slots(self):
@@ -616,64 +631,63 @@ class TrainStep:
         accumulate (mfnerf_grid_encode_bw_binned_adam + mfnerf_adam_step_fixed_partial)."""
         return self._binned() and self.shard is None and load().mfnerf_grid_binned_first_value(self.desc) >= 0
 
-    def _adam_fused_args(self):
-        c = self.cfg
-        amp = self._amp_ptr()
-        return AdamFused(params=self.params.data_ptr(), m=self.m.data_ptr(), v=self.v.data_ptr(),
-                         p16=self.p16.data_ptr(), table_offset=self.off_table, lr=float(c.lr), beta1=0.9,
-                         beta2=0.999, eps=float(c.eps), step_dev=self.step_dev.data_ptr(),
-                         lr_dev=self.lr_dev.data_ptr(), amp=amp.value if amp is not None else None)
+    def _adam_args(self):
+        """Every Adam entry point's (lr, beta1, beta2, eps), (device step count, device lr, GradScaler state)."""
+        return (float(self.cfg.lr), *ADAM_BETAS, self.cfg.eps), (ptr(self.step_dev), ptr(self.lr_dev), self._amp_ptr())
+
+    def _open_gate(self, gate, in_launch):
+        """A scatter opens the side stream's gate as it starts: its dense-level launch's first workgroup
+        (in_launch: the entry point takes the pointer), else a signal kernel just before it.  Counted."""
+        if gate is not None:
+            self._gate_opened += 1
+            if not in_launch:
+                call("mfnerf_gate_signal", gate, stream())
+
+    def _scatter_args(self, mb, q):
+        """(samples, count, box, grid, dL/dfeat), table gradient, the binned forms' (workspace, slots, level_l1)."""
+        t = self.parts[q]
+        return ((*self._enc_args(mb, q), ptr(t.dfeat)), ptr(self.grads[self.off_table:]),
+                (ptr(t.grid_ws), self._bin_slots(), ptr(self._level_l1)))
 
     def _grid_bw(self, mb, q, fuse_adam=False, gate=None):
         """Part q's hash-table gradient scatter (the dominant kernel, alone so it can be timed);
         fuse_adam: with the partitioned tables' Adam step (then _finish_update(partial=True));
-        fuse_adam="all": with the whole optimizer step and the MLP repack.  gate (the side stream's
-        gate pointer): opened as the scatter starts -- by the dense-level launch's first workgroup
-        where the launch takes a gate, else by a signal kernel of its own just before it."""
-        t, m = self.parts[q], mb.part[q]
-        if gate is not None:
-            self._gate_opened += 1
-        if self._binned() and fuse_adam == "all":
-            self._fused_args = self._adam_fused_args()  # kept alive: graphs capture the call
-            call("mfnerf_grid_encode_bw_binned_adam_all", ptr(m.xyzs), self.cap_p, ptr(m.counter), self.x_min,
-                 self.x_range, self.desc, ptr(t.dfeat), ptr(self.grads), self.n_alloc, ptr(t.grid_ws),
-                 self._bin_slots(), ptr(self._level_l1), ctypes.byref(self._fused_args), ptr(self.step_dev),
-                 self._amp_ptr(), ptr(self.packed), self.cfg.rgb_width, gate, stream())
-            return
-        if gate is not None:
-            call("mfnerf_gate_signal", gate, stream())
-        if self._binned() and fuse_adam:
-            self._fused_args = self._adam_fused_args()  # kept alive: graphs capture the call
-            call("mfnerf_grid_encode_bw_binned_adam", ptr(m.xyzs), self.cap_p, ptr(m.counter), self.x_min,
-                 self.x_range, self.desc, ptr(t.dfeat), ptr(self.grads[self.off_table:]), ptr(t.grid_ws),
-                 self._bin_slots(), ptr(self._level_l1), ctypes.byref(self._fused_args), stream())
-            return
-        if self._binned():
+        fuse_adam="all": with the whole optimizer step and the MLP repack.  gate: see _open_gate."""
+        src, table, (ws, slots, l1) = self._scatter_args(mb, q)
+        binned = self._binned()
+        fuse_all = binned and fuse_adam == "all"
+        self._open_gate(gate, in_launch=fuse_all)
+        if binned and fuse_adam:
+            (lr, beta1, beta2, eps), (step_dev, lr_dev, amp) = self._adam_args()
+            self._fused_args = AdamFused(  # kept alive: graphs capture the call
+                params=self.params.data_ptr(), m=self.m.data_ptr(), v=self.v.data_ptr(), p16=self.p16.data_ptr(),
+                table_offset=self.off_table, lr=lr, beta1=beta1, beta2=beta2, eps=eps, step_dev=step_dev.value,
+                lr_dev=lr_dev.value, amp=amp.value if amp is not None else None)
+        if fuse_all:
+            call("mfnerf_grid_encode_bw_binned_adam_all", *src, ptr(self.grads), self.n_alloc, ws, slots, l1,
+                 ctypes.byref(self._fused_args), ptr(self.step_dev), self._amp_ptr(), ptr(self.packed),
+                 self.cfg.rgb_width, gate, stream())
+        elif binned and fuse_adam:
+            call("mfnerf_grid_encode_bw_binned_adam", *src, table, ws, slots, l1, ctypes.byref(self._fused_args),
+                 stream())
+        elif binned:
             # both parts in sequence on this stream: the coarse levels' atomics, then the fine levels'
             # partitioned sums (the two on separate streams inside the graphs measured 1.32 vs
             # 0.87 ms per step: the extra branch slowed every kernel beside it)
-            call("mfnerf_grid_encode_bw_binned", ptr(m.xyzs), self.cap_p, ptr(m.counter), self.x_min, self.x_range,
-                 self.desc, ptr(t.dfeat), ptr(self.grads[self.off_table:]), ptr(t.grid_ws), self._bin_slots(),
-                 ptr(self._level_l1), 3, stream())
-            return
-        call("mfnerf_grid_encode_bw_scatter", ptr(m.xyzs), self.cap_p, ptr(m.counter), self.x_min, self.x_range,
-             self.desc, ptr(t.dfeat), ptr(self.grads[self.off_table:]), ptr(t.grid_ws),
-             ptr(self._level_l1) if self._fixed() else None, stream())
+            call("mfnerf_grid_encode_bw_binned", *src, table, ws, slots, l1, 3, stream())
+        else:
+            call("mfnerf_grid_encode_bw_scatter", *src, table, ws, l1 if self._fixed() else None, stream())
 
     def _store_fold(self):
         """Sharded, one part, partitioned scatter whose float finish overwrites every table value
         before the partitioned tables (they are all dense-prefix values): the weight-gradient fold
-        stores instead of adding and the step zeroes no gradient prefix (one fill launch less)."""
-        v = getattr(self, "_store_fold_v", None)
-        if v is None:
-            lib = load()
-            n_dw = lib.mfnerf_field_bw_workspace(0, self.cfg.rgb_width) // (4 * lib.mfnerf_field_bw_slab_rows(
-                self.cfg.rgb_width))
-            v = (self.shard is not None and self.n_parts == 1 and self._binned() and self._fixed()
-                 and self.off_table == n_dw
-                 and lib.mfnerf_grid_binned_first_value(self.desc) == lib.mfnerf_grid_dense_values(self.desc))
-            self._store_fold_v = v
-        return v
+        stores instead of adding and the step zeroes no gradient prefix (one fill launch less).
+        Evaluated once per sharding: _store_fold_v."""
+        lib, w = load(), self.cfg.rgb_width
+        n_dw = lib.mfnerf_field_bw_workspace(0, w) // (4 * lib.mfnerf_field_bw_slab_rows(w))
+        return (self.shard is not None and self.n_parts == 1 and self._binned() and self._fixed()
+                and self.off_table == n_dw
+                and lib.mfnerf_grid_binned_first_value(self.desc) == lib.mfnerf_grid_dense_values(self.desc))
 
     def _grad_zero_end(self):
         """Gradient values a step must find zero: all of them, or with the binned scatter only those
@@ -682,30 +696,6 @@ class TrainStep:
         if self._binned():
             return self.off_table + load().mfnerf_grid_binned_first_value(self.desc)
         return self.n_alloc
-
-    def _grid_bw_float(self, mb, zero_l1=True, gate=None, shard_flag=None):
-        """Data parallel, one part: the table gradient scattered and finished to floats for the
-        exchange (binned: the accumulate writes the partitioned tables' floats and one finish pass
-        covers the rest, mfnerf_grid_encode_bw_binned_float), level_l1 zeroed after use (zero_l1
-        False: the sharded Adam's last workgroup zeroes it, _adam_shard); gate: the side stream's
-        gate pointer, opened as the dense-level launch starts (no signal launch of its own);
-        shard_flag (flag pointer, shards, shard length): mfnerf_flag_to_shards folded into the
-        float finish when it has a table prefix to ride -- returns True when it was."""
-        if not self._binned():
-            self._grid_bw(mb, 0, gate=gate)
-            self._grid_finish(0)
-            return False
-        t, m = self.parts[0], mb.part[0]
-        if gate is not None:
-            self._gate_opened += 1
-        fold_flag = shard_flag is not None and load().mfnerf_grid_binned_first_value(self.desc) > 0
-        fl, fw, fs = shard_flag if fold_flag else (None, 0, 0)
-        call("mfnerf_grid_encode_bw_binned_float", ptr(m.xyzs), self.cap_p, ptr(m.counter), self.x_min,
-             self.x_range, self.desc, ptr(t.dfeat), ptr(self.grads[self.off_table:]), ptr(t.grid_ws),
-             self._bin_slots(), ptr(self._level_l1), gate, fl, fw, fs, self.off_table, stream())
-        if zero_l1:
-            self._level_l1.zero_()
-        return fold_flag
 
     def _grid_finish(self, q):
         """Fold part q's private copies of the coarse levels / convert the fixed-point sums."""
@@ -722,38 +712,29 @@ class TrainStep:
     def _adam(self, grads, lo, hi, zero_grads):
         """Adam over params[lo:hi] with grads (hi-lo), refreshing p16[lo:hi]; a no-op (but for the
         zeroing) when the step's non-finite flag is up (raised by field_bw, cleared by the call)."""
-        c = self.cfg
+        hyper, dev = self._adam_args()
         call("mfnerf_adam_step", ptr(self.params[lo:hi]), ptr(grads), ptr(self.m), ptr(self.v), ptr(self.p16[lo:hi]),
-             hi - lo, float(c.lr), 0.9, 0.999, c.eps, 1.0, 0, ptr(self.step_dev), ptr(self.lr_dev),
-             self._amp_ptr(), int(zero_grads), stream())
-
-    def _adam_shard(self):
-        """The sharded update after the reduce-scatter with the exchanged non-finite flag read from
-        the shard itself and level_l1 zeroed by its last workgroup (mfnerf_adam_step_shard: the
-        flag_from_shard launch and the level_l1 fill folded in)."""
-        c, (_, lo, hi) = self.cfg, self.shard
-        call("mfnerf_adam_step_shard", ptr(self.params[lo:hi]), ptr(self.g_shard), ptr(self.m), ptr(self.v),
-             ptr(self.p16[lo:hi]), hi - lo, float(c.lr), 0.9, 0.999, c.eps, 1.0, ptr(self.step_dev), ptr(self.lr_dev),
-             self._amp_ptr(), ptr(self._level_l1), self._level_l1.numel(), stream())
+             hi - lo, *hyper, 1.0, 0, *dev, int(zero_grads), stream())
 
     def _finish_update(self, partial=False):
-        """Unsharded, no exchange, fixed-point table gradient: the finish (convert) and Adam in one
-        pass (mfnerf_adam_step_fixed), then the MLP weight repack.  partial: after a fused
-        _grid_bw, only the values before the partitioned tables (all of them if a slot overflowed)."""
-        c = self.cfg
+        """One part, unsharded, no exchange, after the scatter.  Fixed-point table gradient: the finish
+        (convert) and Adam in one pass (mfnerf_adam_step_fixed), then the MLP weight repack; float
+        atomics: the finish, then the plain update.  partial: after a fused _grid_bw, only the values
+        before the partitioned tables (all of them if a slot overflowed)."""
+        if not self._fixed():
+            self._grid_finish(0)
+            self._update()
+            return
+        ws, (hyper, dev) = self.parts[0].grid_ws, self._adam_args()
+        args = (ptr(self.params), ptr(self.grads), ptr(self.m), ptr(self.v), ptr(self.p16), self.n_alloc,
+                self.off_table, self.desc, ptr(ws), ptr(self._level_l1), *hyper, *dev)
         if partial:
-            ws = self.parts[0].grid_ws
             ovf = ctypes.c_void_p(ws.data_ptr() + load().mfnerf_grid_encode_bw_binned_flag_offset(
                 self.desc, self._bin_slots()))
-            call("mfnerf_adam_step_fixed_partial", ptr(self.params), ptr(self.grads), ptr(self.m), ptr(self.v),
-                 ptr(self.p16), self.n_alloc, self.off_table, self.desc, ptr(ws), ptr(self._level_l1),
-                 float(c.lr), 0.9, 0.999, c.eps, ptr(self.step_dev), ptr(self.lr_dev), self._amp_ptr(),
+            call("mfnerf_adam_step_fixed_partial", *args,
                  self.off_table + load().mfnerf_grid_binned_first_value(self.desc), ovf, stream())
         else:
-            call("mfnerf_adam_step_fixed", ptr(self.params), ptr(self.grads), ptr(self.m), ptr(self.v),
-                 ptr(self.p16), self.n_alloc, self.off_table, self.desc, ptr(self.parts[0].grid_ws),
-                 ptr(self._level_l1), float(c.lr), 0.9, 0.999, c.eps, ptr(self.step_dev), ptr(self.lr_dev),
-                 self._amp_ptr(), stream())
+            call("mfnerf_adam_step_fixed", *args, stream())
         self._pack()
 
     def _update(self):
@@ -761,11 +742,6 @@ class TrainStep:
         MLP weight repack (unsharded)."""
         self._adam(self.grads, 0, self.n_alloc, True)
         self._pack()
-
-    def _shard_adam(self, adam):
-        """Sharded: the flag already holds the union over ranks (carried through the
-        reduce-scatter, dp.sharded_update), so every rank takes the same decision."""
-        adam()
 
     def full_params(self):
         """The fp32 master parameters (all-gathered over ranks when the optimizer is sharded)."""
@@ -789,32 +765,33 @@ class TrainStep:
         """Optimizer steps skipped on non-finite gradients so far (host read)."""
         return int(self.finite_status[1])
 
-    def _optimize(self, exchange, adam=None, pack=None):
-        """The update half of a step.  Sharded: reduce-scatter -> Adam on the shard -> all-gather
-        fp16 -> repack; else: exchange(grads) (all-reduce, optional) -> Adam -> repack.  adam/pack
-        replace the eager launches by graph replays."""
-        from . import dp
+    def _count_update(self):
+        """adam_step, the host's mirror of Adam's device-side step count: one more update issued."""
         self.adam_step += 1
+
+    def _optimize(self, exchange, graphs=None):
+        """The update half of a step.  Sharded: reduce-scatter -> Adam on the shard -> all-gather
+        fp16 -> repack; else: exchange(grads) (all-reduce, optional) -> Adam -> repack.  graphs (a
+        replay's): Adam and the repack are replays of the captured "adam" + "pack" / "update"."""
+        from . import dp
+        self._count_update()
+        flag = self.finite_status[:1] if self._amp_on() else None
         if self.shard is not None:
             rank, lo, hi = self.shard
-            dp.sharded_update(self.grads, self.g_shard, self.p16, rank,
-                              adam or (lambda g: self._shard_adam(lambda: self._adam(g, lo, hi, False))),
-                              flag=self.finite_status[:1] if self._amp_on() else None)
-            (pack or self._pack)()
-        else:
-            if exchange is not None:
-                # the non-finite flag rides the all-reduce: NaN in element 0 when set, read back
-                flag = self.finite_status[:1] if self._amp_on() else None
-                if flag is not None:
-                    call("mfnerf_flag_to_shards", ptr(self.grads), 1, self.n_alloc, ptr(flag), stream())
-                exchange(self.grads)
-                if flag is not None:
-                    call("mfnerf_flag_from_shard", ptr(self.grads), ptr(flag), stream())
-            if adam is not None:
-                adam(None)
-                (pack or (lambda: None))()
-            else:
-                self._update()
+
+            def adam(g_shard):  # the flag holds the union over ranks by now (it rode the reduce-scatter)
+                graphs["adam"].replay() if graphs else self._adam(g_shard, lo, hi, False)
+            dp.sharded_update(self.grads, self.g_shard, self.p16, rank, adam, flag=flag)
+            graphs["pack"].replay() if graphs else self._pack()
+            return
+        if exchange is not None:
+            # the non-finite flag rides the all-reduce: NaN in element 0 when set, read back
+            if flag is not None:
+                call("mfnerf_flag_to_shards", ptr(self.grads), 1, self.n_alloc, ptr(flag), stream())
+            exchange(self.grads)
+            if flag is not None:
+                call("mfnerf_flag_from_shard", ptr(self.grads), ptr(flag), stream())
+        graphs["update"].replay() if graphs else self._update()
 
     def _check_bg(self, *given):
         """bg= / next_bg= are for a step that passes its batches with random_bg on (ignored on a
@@ -834,7 +811,7 @@ class TrainStep:
         Adam step, no repack; for inspection).  random_bg: the step's background colour comes with
         the dataset's draw; for a passed batch it is bg (3 values) or, bg=None, three draws from the
         step's generator after the noise."""
-        mark = mark or (lambda name: None)
+        mark = mark or _nomark
         self._check_bg(bg)
         if self.cfg.refine_poses:
             self._check_refine(exchange)
@@ -850,27 +827,19 @@ class TrainStep:
         self.last_batch = batch
         self._primed = False  # a pipelined replay() must march its own batch next
         self._march(batch, mb, mark, prepped=prepped, noise=noise, bg=bg)
-        dp = self.shard is not None or exchange is not None
-        for q in range(self.n_parts):
-            self._chain(batch, mb, q, mark)
-            if dp and self.n_parts == 1:  # the data-parallel step's form (as the captured dp_pre)
-                self._grid_bw_float(mb)
+        if self.n_parts == 1 and self._dp(exchange):
+            self._dp_backward(batch, mb, mark)
+        else:
+            for q in range(self.n_parts):
+                self._chain(batch, mb, q, mark)
+                self._grid_bw(mb, q)
                 mark("grid_bw")
+                self._grid_finish(q)
                 mark("grid_finish")
-                continue
-            self._grid_bw(mb, q)
-            mark("grid_bw")
-            self._grid_finish(q)
-            mark("grid_finish")
         self._reduce_parts()
         if optimize:
             self._optimize(exchange)
         mark("update")
-
-    def optimizer(self, lr=None, exchange=None):
-        if lr is not None:
-            self.set_lr(lr)
-        self._optimize(exchange)
 
     def set_lr(self, lr):
         """Device-resident learning rate (train.py:137-142 cosine schedule), read by Adam."""
@@ -878,6 +847,104 @@ class TrainStep:
 
     def step(self, batch: Batch):
         self.run(batch)
+
+    # ------------------------------- the step's forms: one body each, launched by run(), recorded by capture()
+    def _dp(self, exchange):
+        """Data parallel: a sharded optimizer, or a gradient exchange between backward and Adam."""
+        return self.shard is not None or exchange is not None
+
+    def _fused_shard(self):
+        """Sharded with amp: one launch reads the exchanged flag, updates and zeroes level_l1."""
+        return self._amp_on() and self.shard is not None
+
+    def _dp_backward(self, batch, mb, mark=_nomark, captured=False):
+        """Data parallel, one part: the chain, then the table gradient scattered and finished to floats
+        for the exchange (binned: the accumulate writes the partitioned tables' floats and one finish
+        pass covers the rest).  Eagerly _flush_pack precedes and _optimize follows, carrying the
+        non-finite flag around its own collective.  The captured form (dp_pre) differs in four ways:
+        it starts with the repack; it opens the gate; the flag rides the collective as NaN in every
+        shard's first value (written by the float finish when it has a table prefix to ride, else by a
+        launch of its own); level_l1 is left to the sharded Adam, whose last workgroup zeroes it."""
+        gate, flag_rides = None, False
+        if captured:
+            self._pack()  # the previous step's all-gathered / updated fp16 weights
+            gate, flag_rides = self._gate_ptr(), self._amp_on()
+            w = self.shard[2] - self.shard[1] if self.shard is not None else self.n_alloc
+            flag, shards = ptr(self.finite_status), (self.n_alloc // w, w)  # (how many, how long)
+        self._chain(batch, mb, 0, mark)
+        if self._binned():
+            src, table, binned_ws = self._scatter_args(mb, 0)
+            self._open_gate(gate, in_launch=True)
+            fold = flag_rides and load().mfnerf_grid_binned_first_value(self.desc) > 0
+            call("mfnerf_grid_encode_bw_binned_float", *src, table, *binned_ws, gate,
+                 *((flag, *shards) if fold else (None, 0, 0)), self.off_table, stream())
+            if not (captured and self._fused_shard()):
+                self._level_l1.zero_()
+            flag_rides = flag_rides and not fold
+        else:
+            self._grid_bw(mb, 0, gate=gate)
+            self._grid_finish(0)
+        if flag_rides:
+            call("mfnerf_flag_to_shards", ptr(self.grads), *shards, flag, stream())
+        mark("grid_bw")
+        mark("grid_finish")
+
+    def _dp_post(self):
+        """After the exchange: the flag back, then Adam on this rank's shard (sharded) or everywhere."""
+        g, lo, hi = (self.g_shard, *self.shard[1:]) if self.shard is not None else (self.grads, 0, self.n_alloc)
+        if self._fused_shard():
+            # mfnerf_adam_step_shard: the flag_from_shard launch and the level_l1 fill folded in
+            hyper, dev = self._adam_args()
+            call("mfnerf_adam_step_shard", ptr(self.params[lo:hi]), ptr(g), ptr(self.m), ptr(self.v),
+                 ptr(self.p16[lo:hi]), hi - lo, *hyper, 1.0, *dev, ptr(self._level_l1), self._level_l1.numel(),
+                 stream())
+            return
+        if self._amp_on():
+            call("mfnerf_flag_from_shard", ptr(g), ptr(self.finite_status), stream())
+        self._adam(g, lo, hi, self.shard is None)
+
+    def _dp_exchange(self, exchange, update):
+        """The collectives around the data-parallel update (update: _dp_post, or its graph's replay)."""
+        from . import dp
+        if self.shard is None:
+            exchange(self.grads)
+            return update()
+        dp.reduce_scatter_mean_(self.g_shard, self.grads)
+        update()
+        dp.all_gather_(self.p16, self.shard[0])
+
+    def _dp_step(self, j):
+        """RCCL on this stream (mfnerf.rccl): the collectives are captured too, and the whole
+        data-parallel step (repack, chain, scatter, exchange, Adam, all-gather) replays as ONE graph
+        -- no host hop between the backward and the update."""
+        from . import dp
+        self._dp_backward(self._static[j], self.mbuf[j], captured=True)
+        self._dp_exchange(dp.allreduce_mean_, self._dp_post)
+
+    def _march_static(self, j, gated=False):
+        """Static set j (the dataset's draw, or what replay() staged) into march buffer set j."""
+        if gated:
+            call("mfnerf_gate_wait", self._gate_ptr(), GATE_TIMEOUT_US, stream())
+        drawn = self.dataset is not None
+        if drawn:
+            self._draw(self._static[j], self.mbuf[j])
+        self._march(self._static[j], self.mbuf[j], _nomark, prepped=drawn,
+                    noise=self._static_noise[j] if self._host_noise else None,
+                    bg=self._static_bg[j] if self._static_bg is not None else None)
+
+    def _step(self, j, whole=True):
+        """The collective-free step on set j.  whole: from the chain, as ONE graph whose scatter opens
+        the device gate where the host used to record the event that starts the next march; else from
+        the scatter on (per-stage steps).  Where the layout allows, the whole optimizer runs inside the
+        scatter's launches (the MLPs' and dense levels' update rides the accumulate's, then the repack)."""
+        gate = self._gate_ptr() if whole else None
+        if whole:
+            self._chain(self._static[j], self.mbuf[j], 0, _nomark)
+        if self._fused_adam_ok():
+            self._grid_bw(self.mbuf[j], 0, fuse_adam="all", gate=gate)
+        else:
+            self._grid_bw(self.mbuf[j], 0, gate=gate)
+            self._finish_update()
 
     # ---------------------------------------------------------------- HIP graphs
     def capture(self, host_noise=False):
@@ -900,142 +967,57 @@ class TrainStep:
         into, so the step graph of set j reads the colour of the batch it trains on while the next
         batch's colour waits in set 1-j.
         Call after at least one eager step (lazy library init happens outside capture)."""
-        N = self.cfg.n_rays
         self._check_refine()
         self._flush_pack()
-        if len(self.mbuf) == 1:
-            self.mbuf.append(self._march_buffers())
-        if self.cfg.refine_poses:
-            self.compose_poses()  # both buffers start from the offsets the eager steps left
-        self._static = [_packed_batch(torch.zeros(3, N, 3, device=self.dev)) for _ in range(2)]
-        self._host_noise = bool(host_noise)
-        self._static_noise = [torch.zeros(N, device=self.dev) for _ in range(2)] if host_noise else None
-        host_bg = host_noise and self._random_bg() and self.dataset is None
-        self._static_bg = [torch.zeros(3, device=self.dev) for _ in range(2)] if host_bg else None
+        self._capture_setup(host_noise)
         torch.cuda.synchronize()
         pool = torch.cuda.graph_pool_handle()
-        nomark = lambda _n: None  # noqa: E731
 
-        def cap(fn, rng=False):
+        def cap(fn, *args, rng=False, **kw):
             g = torch.cuda.CUDAGraph()
             if rng:
                 g.register_generator_state(self.gen)
             with torch.cuda.graph(g, pool=pool):
-                fn()
+                fn(*args, **kw)
             return g
 
-        P = self.n_parts
-        def march(j):
-            if self.dataset is not None:
-                self._draw(self._static[j], self.mbuf[j])
-            self._march(self._static[j], self.mbuf[j], nomark, prepped=self.dataset is not None,
-                        noise=self._static_noise[j] if host_noise else None,
-                        bg=self._static_bg[j] if host_bg else None)
-
-        self.graphs = {
-            "march": [cap(lambda j=j: march(j), rng=True) for j in range(2)],
-            "chain": [[cap(lambda j=j, q=q: self._chain(self._static[j], self.mbuf[j], q, nomark)) for q in range(P)]
-                      for j in range(2)],
-            "grid_bw": [[cap(lambda j=j, q=q: self._grid_bw(self.mbuf[j], q)) for q in range(P)] for j in range(2)],
-            "finish": [cap(lambda q=q: self._grid_finish(q)) for q in range(P)],
-            "reduce": cap(self._reduce_parts) if P > 1 else None,
-        }
-        # one part: the next step's march waits on the side stream for the gate the step graph opens
-        # as its scatter begins (the dense-level launch's first workgroup, or a signal kernel)
-        gated = P == 1
-        self._gate = torch.zeros(4, dtype=torch.int32, device=self.dev)  # {signals, waits, -, timeouts}
-        gp = ptr(self._gate) if gated else None
-        self._gate_opened = 0
-        if gated:
-            self.graphs["march_gated"] = [
-                cap(lambda j=j: (call("mfnerf_gate_wait", gp, GATE_TIMEOUT_US, stream()), march(j)), rng=True)
-                for j in range(2)]
-        amp = self._amp_on()
-        self.graphs["pack"] = cap(self._pack)
-        if self.shard is not None:
-            rank, lo, hi = self.shard
-            self.graphs["adam"] = cap(lambda: self._adam(self.g_shard, lo, hi, False))
-        else:
-            self.graphs["update"] = cap(self._update)
-        if P == 1:
-            # data parallel: the step up to the exchange, then the update after it
-            w = self.shard[2] - self.shard[1] if self.shard is not None else self.n_alloc
-            n_sh = self.n_alloc // w
-            # sharded with amp: one launch reads the exchanged flag, updates and zeroes level_l1
-            fused_shard = amp and self.shard is not None
-
-            def dp_pre(j):
-                self._pack()  # the previous step's all-gathered / updated fp16 weights
-                self._chain(self._static[j], self.mbuf[j], 0, nomark)
-                # the non-finite flag rides the collective: NaN into every shard's first value (by
-                # the float finish when it can, else a launch of its own)
-                sf = (ptr(self.finite_status), n_sh, w) if amp else None
-                folded = self._grid_bw_float(self.mbuf[j], zero_l1=not fused_shard, gate=gp, shard_flag=sf)
-                if amp and not folded:
-                    call("mfnerf_flag_to_shards", ptr(self.grads), n_sh, w, ptr(self.finite_status), stream())
-
-            def dp_post():
-                if fused_shard:
-                    self._adam_shard()
-                elif self.shard is not None:
-                    if amp:
-                        call("mfnerf_flag_from_shard", ptr(self.g_shard), ptr(self.finite_status), stream())
-                    self._adam(self.g_shard, self.shard[1], self.shard[2], False)
-                else:
-                    if amp:
-                        call("mfnerf_flag_from_shard", ptr(self.grads), ptr(self.finite_status), stream())
-                    self._adam(self.grads, 0, self.n_alloc, True)
-            self.graphs["dp_pre"] = [cap(lambda j=j: dp_pre(j)) for j in range(2)]
-            self.graphs["dp_post"] = cap(dp_post)
-            from . import dp as _dp
-            if _dp.direct_rccl() is not None:
-                # RCCL on this stream (mfnerf.rccl): the collectives are captured too, and the whole
-                # data-parallel step (repack, chain, scatter, exchange, Adam, all-gather) replays as
-                # ONE graph -- no host hop between the backward and the update
-                def dp_step(j):
-                    dp_pre(j)
-                    if self.shard is not None:
-                        _dp.reduce_scatter_mean_(self.g_shard, self.grads)
-                        dp_post()
-                        _dp.all_gather_(self.p16, self.shard[0])
-                    else:
-                        _dp.allreduce_mean_(self.grads)
-                        dp_post()
-                self.graphs["dp_step"] = [cap(lambda j=j: dp_step(j)) for j in range(2)]
-        if self.shard is None and P == 1:
-            tail = self._finish_update if self._fixed() else lambda: (self._grid_finish(0), self._update())
-            self.graphs["finish_update"] = cap(tail)
-            fuse = self._fixed() and self._fused_adam_ok()
-            # the scatter with the optimizer (one graph transition less) for untimed steps
-            if fuse:  # the whole optimizer inside the scatter's launches
-                self.graphs["grid_bw_tail"] = [cap(lambda j=j: self._fused_tail(j)) for j in range(2)]
-            else:
-                self.graphs["grid_bw_tail"] = [cap(lambda j=j: (self._grid_bw(self.mbuf[j], 0), tail()))
-                                               for j in range(2)]
-
-            # the whole step as ONE graph: the scatter opens the device gate where the host used to
-            # record the event that starts the next march
-            def step(j):
-                self._chain(self._static[j], self.mbuf[j], 0, nomark)
-                if fuse:
-                    self._fused_tail(j, gate=gp)
-                else:
-                    self._grid_bw(self.mbuf[j], 0, gate=gp)
-                    tail()
-            self.graphs["step"] = [cap(lambda j=j: step(j)) for j in range(2)]
+        # (the order of the captures is kept as it was: they share one memory pool)
+        self.graphs = self._capture_stages(cap)
+        if self.n_parts == 1:
+            self.graphs.update(self._capture_dp(cap))
+            if self.shard is None:
+                self.graphs.update(self._capture_one_graph(cap))
         n_gated = 2 * sum(1 for k in ("step", "dp_pre", "dp_step") if self.graphs.get(k) is not None)
-        if gated and self._gate_opened != n_gated:
+        if self._gate is not None and self._gate_opened != n_gated:
             # every gated graph must open the gate exactly once, or each gated march would spin for
             # GATE_TIMEOUT_US before starting
             raise RuntimeError(f"gated graphs opened the gate {self._gate_opened} times, not {n_gated}")
         torch.cuda.synchronize()
+
+    def _capture_setup(self, host_noise):
+        """What replay() fills (second march buffer set, static batches, host_noise's staged noise / colour)
+        and orders the graphs with (the gated march's gate, streams, events); set 0 first, unprimed."""
+        N, dev, P = self.cfg.n_rays, self.dev, self.n_parts
+        if len(self.mbuf) == 1:
+            self.mbuf.append(self._march_buffers())
+        if self.cfg.refine_poses:
+            self.compose_poses()  # both buffers start from the offsets the eager steps left
+        self._static = [_packed_batch(torch.zeros(3, N, 3, device=dev)) for _ in range(2)]
+        self._host_noise = bool(host_noise)
+        self._static_noise = [torch.zeros(N, device=dev) for _ in range(2)] if host_noise else None
+        host_bg = host_noise and self._random_bg() and self.dataset is None
+        self._static_bg = [torch.zeros(3, device=dev) for _ in range(2)] if host_bg else None
+        # one part: the next step's march waits on the side stream for the gate the step graph opens
+        # as its scatter begins (the dense-level launch's first workgroup, or a signal kernel)
+        self._gate = torch.zeros(4, dtype=torch.int32, device=dev) if P == 1 else None
+        self._gate_opened = 0
         # the side stream at normal queue priority: a high-priority one measured the same alone
         # (0.601 vs 0.601 ms/step) but, once an RCCL communicator exists in the process, it ran every
         # step at 1.10 ms (kernels on the main queue 2-7x slower; the extra streams share hardware
         # queues) -- the data-parallel step would pay it on every rank.  No priority below normal
         # exists here (torch.cuda.Stream.priority_range() is (0, -1) on this ROCm, r4m).
-        self._side = torch.cuda.Stream(device=self.dev, priority=0)
-        self._part_streams = [None] + [torch.cuda.Stream(device=self.dev) for _ in range(P - 1)]
+        self._side = torch.cuda.Stream(device=dev, priority=0)
+        self._part_streams = [None] + [torch.cuda.Stream(device=dev) for _ in range(P - 1)]
         self._ev_march = [torch.cuda.Event(), torch.cuda.Event()]
         self._ev_start = torch.cuda.Event()
         self._ev_chain = [torch.cuda.Event() for _ in range(P)]
@@ -1043,37 +1025,63 @@ class TrainStep:
         self._parity = 0
         self._primed = False
 
+    def _gate_ptr(self):
+        return ptr(self._gate) if self._gate is not None else None
+
+    def _capture_stages(self, cap):
+        """The per-stage graphs: march (and, one part, gated march), chain, scatter, finish, reduce, update."""
+        P, sets = self.n_parts, range(2)
+        g = {
+            "march": [cap(self._march_static, j, rng=True) for j in sets],
+            "chain": [[cap(self._chain, self._static[j], self.mbuf[j], q, _nomark) for q in range(P)] for j in sets],
+            "grid_bw": [[cap(self._grid_bw, self.mbuf[j], q) for q in range(P)] for j in sets],
+            "finish": [cap(self._grid_finish, q) for q in range(P)],
+            "reduce": cap(self._reduce_parts) if P > 1 else None,
+        }
+        if self._gate is not None:
+            g["march_gated"] = [cap(self._march_static, j, gated=True, rng=True) for j in sets]
+        g["pack"] = cap(self._pack)
+        if self.shard is not None:
+            g["adam"] = cap(self._adam, self.g_shard, self.shard[1], self.shard[2], False)
+        else:
+            g["update"] = cap(self._update)
+        return g
+
+    def _capture_dp(self, cap):
+        """One part, data parallel: up to the exchange, after it and, direct RCCL, both around it as one graph."""
+        from . import dp
+        g = {"dp_pre": [cap(self._dp_backward, self._static[j], self.mbuf[j], captured=True) for j in range(2)],
+             "dp_post": cap(self._dp_post)}
+        if dp.direct_rccl() is not None:
+            g["dp_step"] = [cap(self._dp_step, j) for j in range(2)]
+        return g
+
+    def _capture_one_graph(self, cap):
+        """One part, no collective: the tail, the scatter with it (untimed per-stage steps), the whole step."""
+        return {"finish_update": cap(self._finish_update),
+                "grid_bw_tail": [cap(self._step, j, whole=False) for j in range(2)],
+                "step": [cap(self._step, j) for j in range(2)]}
+
     def gate_timeouts(self):
         """Gated marches that started on the gate's timeout instead of its signal (gate.hip's gate[3],
         cumulative; a host read, so it synchronises): non-zero means a step paid up to GATE_TIMEOUT_US
         -- e.g. the side stream shares a hardware queue with the stream that signals."""
-        g = getattr(self, "_gate", None)
-        return 0 if g is None else int(g[3])
-
-    def _fused_tail(self, j, gate=None):
-        """The replayed collective-free tail: the scatter with every Adam update in its launches
-        (mfnerf_grid_encode_bw_binned_adam_all: the MLPs' and dense levels' update rides the
-        accumulate's launch) and the MLP repack; gate: opened as the scatter starts."""
-        self._grid_bw(self.mbuf[j], 0, fuse_adam="all", gate=gate)
-
-    def _stage_batch(self, j, batch):
-        dst = self._static[j]
-        if getattr(batch, "buf", None) is not None:
-            dst.buf.copy_(batch.buf)
-        else:
-            for d, s_ in zip((dst.rays_o, dst.rays_d, dst.rgb), (batch.rays_o, batch.rays_d, batch.rgb)):
-                d.copy_(s_)
+        return 0 if self._gate is None else int(self._gate[3])
 
     def _march_on_side(self, j, batch, after, gated=False, noise=None, bg=None):
         """Copy batch (and, captured with host_noise, its perturbation and, random_bg without a dataset,
-        its background colour) into static set j and march
-        it on the side stream once `after` (an event on the main stream) has passed: set j's buffers
-        were last read two steps back.  gated: the march graph first waits (a polling wave, at most
-        GATE_TIMEOUT_US) for the step graph's gate signal (placement only)."""
+        its background colour) into static set j and march it on the side stream once `after` (an
+        event on the main stream) has passed: set j's buffers were last read two steps back.  gated:
+        the march graph first waits (a polling wave, at most GATE_TIMEOUT_US) for the step graph's
+        gate signal (placement only)."""
         self._side.wait_event(after)
         with torch.cuda.stream(self._side):
-            if batch is not None:
-                self._stage_batch(j, batch)
+            dst = self._static[j]
+            if batch is not None and batch.buf is not None:
+                dst.buf.copy_(batch.buf)
+            elif batch is not None:
+                for d, s_ in zip((dst.rays_o, dst.rays_d, dst.rgb), (batch.rays_o, batch.rays_d, batch.rgb)):
+                    d.copy_(s_)
             if self._host_noise:
                 if noise is None:
                     raise ValueError("captured with host_noise: pass noise= / next_noise= to replay()")
@@ -1097,11 +1105,9 @@ class TrainStep:
         grid_bw, end after each part's grid_bw (that step runs the per-stage graphs).
         noise / next_noise: the perturbations of batch / next_batch (capture(host_noise=True));
         bg / next_bg: their background colours (random_bg, capture(host_noise=True), no dataset)."""
-        from . import dp
-        g, j, P = self.graphs, self._parity, self.n_parts
+        j = self._parity
         self._check_refine(exchange)
         self._check_bg(bg, next_bg)
-        dp_mode = self.shard is not None or exchange is not None
         if self.dataset is not None:
             batch = None
             if prefetch is None:
@@ -1114,41 +1120,42 @@ class TrainStep:
         self._ev_start.record(main)
         if not self._primed:
             self._march_on_side(j, batch, self._ev_start, noise=noise, bg=bg)
-        one_graph = P == 1 and grid_bw_events is None and prefetch and g.get("march_gated") is not None
-        if one_graph and (dp_mode or g.get("step") is not None):
-            # set 1-j was last read by the previous step, all of which precedes _ev_start
-            main.wait_event(self._ev_march[j])
-            self._use(self.mbuf[j])
-            self.last_batch = self._static[j]
-            self.adam_step += 1
-            if not dp_mode:  # one graph for the step; the next march starts at its gate signal
-                g["step"][j].replay()
-                self._march_on_side(1 - j, next_batch, self._ev_start, gated=True, noise=next_noise, bg=next_bg)
-            elif g.get("dp_step") is not None and (self.shard is not None or exchange is dp.allreduce_mean_):
-                # the whole data-parallel step, collectives included, as one graph (direct RCCL)
-                g["dp_step"][j].replay()
-                self._march_on_side(1 - j, next_batch, self._ev_start, gated=True, noise=next_noise, bg=next_bg)
-                self._stale_pack = True  # the next step's graph starts with the repack
-            else:
-                # [repack] chain, scatter, float gradient, flag -> collective -> Adam -> (all-gather)
-                g["dp_pre"][j].replay()
-                self._march_on_side(1 - j, next_batch, self._ev_start, gated=True, noise=next_noise, bg=next_bg)
-                if self.shard is not None:
-                    dp.reduce_scatter_mean_(self.g_shard, self.grads)
-                    g["dp_post"].replay()
-                    dp.all_gather_(self.p16, self.shard[0])
-                else:
-                    exchange(self.grads)
-                    g["dp_post"].replay()
-                self._stale_pack = True  # the next step's dp_pre (or the pack graph) repacks
-            self._parity = 1 - j
-            self._primed = True
-            return
-        fuse_tail = g.get("finish_update") is not None and not dp_mode
-        self._flush_pack()
-        main.wait_event(self._ev_march[j])
         self._use(self.mbuf[j])
         self.last_batch = self._static[j]
+        nxt = dict(batch=next_batch, noise=next_noise, bg=next_bg)
+        # one part, prefetching, no scatter to time: the step is one graph (two around a host-issued
+        # collective) and the next march starts at its gate signal; else the per-stage graphs
+        if self._gate is not None and grid_bw_events is None and prefetch:
+            self._replay_one_graph(j, main, exchange, nxt)
+        else:
+            self._replay_stages(j, main, exchange, grid_bw_events, nxt if prefetch else None)
+        self._parity = 1 - j
+        self._primed = bool(prefetch)
+
+    def _replay_one_graph(self, j, main, exchange, nxt):
+        """Set j's step as one graph -- "step", or data parallel "dp_step" (direct RCCL: collectives
+        included) or "dp_pre" -> collective -> "dp_post" -> (all-gather) -- with set 1-j's gated march
+        issued behind it on the side stream."""
+        from . import dp
+        g, dp_mode = self.graphs, self._dp(exchange)
+        # set 1-j was last read by the previous step, all of which precedes _ev_start
+        main.wait_event(self._ev_march[j])
+        self._count_update()
+        key = "dp_pre" if dp_mode else "step"
+        if dp_mode and g.get("dp_step") is not None and (self.shard is not None or exchange is dp.allreduce_mean_):
+            key = "dp_step"  # direct RCCL: the collectives are in the graph
+        g[key][j].replay()
+        self._march_on_side(1 - j, after=self._ev_start, gated=True, **nxt)
+        if key == "dp_pre":
+            self._dp_exchange(exchange, g["dp_post"].replay)
+        self._stale_pack = dp_mode  # the next step's dp_pre / dp_step graph (or _flush_pack) repacks
+
+    def _replay_stages(self, j, main, exchange, grid_bw_events, nxt):
+        """Set j's step from the per-stage graphs, part q > 0 on its own stream; nxt: set 1-j's march or None."""
+        g, P, timed = self.graphs, self.n_parts, grid_bw_events is not None
+        fuse_tail = P == 1 and not self._dp(exchange)  # the collective-free tail graphs exist and apply
+        self._flush_pack()
+        main.wait_event(self._ev_march[j])
         for q in range(P):
             sq = main if q == 0 else self._part_streams[q]
             if q > 0:
@@ -1156,47 +1163,39 @@ class TrainStep:
             with torch.cuda.stream(sq):
                 g["chain"][j][q].replay()
                 self._ev_chain[q].record(sq)
-                if q == P - 1 and prefetch:
+                if q == P - 1 and nxt is not None:
                     # set 1-j was last read by the previous step, which this chain follows; waiting
                     # for the last chain puts the march under the grid_bw scatters, not the chains
-                    self._march_on_side(1 - j, next_batch, self._ev_chain[q], noise=next_noise, bg=next_bg)
-                if fuse_tail and grid_bw_events is None:
+                    self._march_on_side(1 - j, after=self._ev_chain[q], **nxt)
+                if fuse_tail and not timed:
                     # P == 1: scatter + convert/Adam + repack as one graph (no event needed between)
-                    self.adam_step += 1
+                    self._count_update()
                     g["grid_bw_tail"][j].replay()
-                    self._ev_part[q].record(sq)
-                    continue
-                if grid_bw_events is not None and q == 0:
-                    grid_bw_events[0].record(sq)
-                g["grid_bw"][j][q].replay()
-                if grid_bw_events is not None:
-                    grid_bw_events[1][q].record(sq)
-                if q > 0:  # the folds read-modify-write the shared gradient: one part at a time
-                    sq.wait_event(self._ev_part[q - 1])
-                if not fuse_tail:
-                    g["finish"][q].replay()
+                else:
+                    if timed and q == 0:
+                        grid_bw_events[0].record(sq)
+                    g["grid_bw"][j][q].replay()
+                    if timed:
+                        grid_bw_events[1][q].record(sq)
+                    if q > 0:  # the folds read-modify-write the shared gradient: one part at a time
+                        sq.wait_event(self._ev_part[q - 1])
+                    if not fuse_tail:
+                        g["finish"][q].replay()
                 self._ev_part[q].record(sq)
         for q in range(1, P):
             main.wait_event(self._ev_part[q])
         if g["reduce"] is not None:
             g["reduce"].replay()
-        if self.shard is not None:
-            self._optimize(None, adam=lambda _g: self._shard_adam(g["adam"].replay),
-                           pack=g["pack"].replay)
-        elif fuse_tail and grid_bw_events is None:
-            pass  # replayed with the scatter above
-        elif fuse_tail:
-            self.adam_step += 1
+        if not fuse_tail:
+            self._optimize(exchange, graphs=g)
+        elif timed:  # (untimed: replayed with the scatter above)
+            self._count_update()
             g["finish_update"].replay()
-        else:
-            self._optimize(exchange, adam=lambda _g: g["update"].replay())
-        self._parity = 1 - j
-        self._primed = bool(prefetch)
 
     # ---------------------------------------------------------------- occupancy (networks.py:157-271)
     def _occ_buffers(self):
         """Scratch for the refresh, sized for the warm-up (all cells) case, allocated once."""
-        if getattr(self, "_occ", None) is None:
+        if self._occ is None:
             lib, c, C, G = load(), self.cfg, self.cascades, self.G
             # one point per distinct drawn cell (mfnerf_occupancy_cells_unique_dev): at most every cell
             n = max(lib.mfnerf_occupancy_points_unique(C, G, G ** 3 // 4, 0), lib.mfnerf_occupancy_points(C, G, 0, 1))
@@ -1240,17 +1239,17 @@ class TrainStep:
     def _occ_launches(self, warmup, decay, count_grid, seed):
         c, C, G, s = self.cfg, self.cascades, self.G, stream()
         o = self._occ_buffers()
-        thr = 0.01 * MAX_SAMPLES / SQRT3
         M = G ** 3 // 4
         # the draws of sample_uniform_and_occupied_cells / get_all_cells reduced to one jittered point per
         # distinct drawn cell (the only sigmas the grid can keep), in row-major cell order; count on the device
         n = load().mfnerf_occupancy_points_unique(C, G, M, int(warmup))
-        call("mfnerf_occupancy_cells_unique_dev", ptr(self.density_grid), C, G, float(c.scale), M, int(warmup), thr,
-             seed, ptr(o.calls), ptr(o.xyz), ptr(o.cell), ptr(o.count), ptr(o.ws), s)
+        call("mfnerf_occupancy_cells_unique_dev", ptr(self.density_grid), C, G, float(c.scale), M, int(warmup),
+             DENSITY_THRESHOLD, seed, ptr(o.calls), ptr(o.xyz), ptr(o.cell), ptr(o.count), ptr(o.ws), s)
         call("mfnerf_grid_encode_fw_planar", ptr(o.xyz), n, ptr(o.count), self.x_min, self.x_range, self.desc,
              ptr(self.p16[self.off_table:]), ptr(o.feat), o.n_max, s)
         # sigma + density_grid_tmp[cell] = sigma in one launch; the update then starts at the decay
         call("mfnerf_field_fw_density_scatter", ptr(o.feat), o.n_max, n, ptr(o.count), ptr(self.packed), c.rgb_width,
              ptr(o.sigma), ptr(o.cell), ptr(o.tmp), s)
         call("mfnerf_occupancy_update_dev", ptr(self.density_grid), None, None, 0, None, C, G, float(decay),
-             ptr(count_grid) if count_grid is not None else None, thr, ptr(o.tmp), 1, ptr(self.bitfield), ptr(o.ws), s)
+             ptr(count_grid) if count_grid is not None else None, DENSITY_THRESHOLD, ptr(o.tmp), 1,
+             ptr(self.bitfield), ptr(o.ws), s)
