@@ -542,6 +542,41 @@ int64_t mfnerf_image_metrics_workspace(int64_t H, int64_t W);
 int mfnerf_image_metrics(const float* pred, const float* target, int64_t H, int64_t W, double* out,
                          void* workspace, mfnerf_stream_t stream);
 
+/* ---------------------------------------------------------------- mesh extraction */
+
+/* A triangle mesh of the density field (test.ipynb, the "mesh" cell: model.density on an N^3 lattice,
+ * then mcubes.marching_cubes(sigma, sigma_threshold) on the host).  Here the lattice stays on the
+ * device and the surface is extracted by marching tetrahedra on the Kuhn split of every cell (six
+ * tetrahedra around the body diagonal; csrc/mesh_table.hpp, generated; specification:
+ * tests/mesh_ref.py) -- the same iso-surface, triangulated differently from mcubes.
+ *
+ * The lattice has nx x ny x nz points (resolution + 1 per axis, each >= 2, nx*ny*nz < 2^31), point
+ * (x, y, z) at linear index (z*ny + y)*nx + x and at world position lo + i*((hi - lo)/(n - 1)) per
+ * axis in fp32.  lo and hi are HOST arrays of 3 floats, read during the call.  A point is inside
+ * when sigma > threshold (NaN outside, +inf inside).  Cells are indexed (z*(ny-1) + y)*(nx-1) + x.
+ *
+ * mfnerf_mesh_lattice_points (test.ipynb mesh cell: the xyz grid handed to model.density): the
+ * world positions of lattice points first .. first+count as xyz (count, 3) f32, so that the density
+ * is evaluated slab by slab (mfnerf_grid_encode_fw + mfnerf_field_fw density_only) and the lattice
+ * never exists as coordinates or features. */
+int mfnerf_mesh_lattice_points(const float* lo, const float* hi, int64_t nx, int64_t ny, int64_t nz, int64_t first,
+                               int64_t count, float* xyz, mfnerf_stream_t stream);
+/* test.ipynb mesh cell, first pass of the extraction: vcount (nx*ny*nz) u8 = the crossing edges each
+ * lattice point owns (0..7: the edges to p + d, d in {0,1}^3 \ {0}, with exactly one end inside);
+ * tcount ((nx-1)*(ny-1)*(nz-1)) u8 = the triangles of each cell (0..12). */
+int mfnerf_mesh_count(const float* sigma, int64_t nx, int64_t ny, int64_t nz, float threshold, uint8_t* vcount,
+                      uint8_t* tcount, mfnerf_stream_t stream);
+/* test.ipynb mesh cell, second pass: voff / toff are the EXCLUSIVE prefix sums (i32) of vcount /
+ * tcount from the same sigma and threshold.  Writes vertices (V, 3) f32 (ordered by owner, then by
+ * edge type 1..7; the vertex of a crossing edge is p0 + t*d, t = (threshold - s0)/(s1 - s0) clamped
+ * to [0, 1], 0.5 when not finite), normals (V, 3) f32 (-grad sigma by central differences of the
+ * lattice, interpolated with t and normalised; (0,0,0) for a zero or non-finite gradient) and faces
+ * (F, 3) i32 (ordered by cell, tetrahedron, triangle; wound so that the normal points from inside to
+ * outside).  The caller sizes the outputs from the counts' totals V and F (both < 2^31). */
+int mfnerf_mesh_emit(const float* sigma, int64_t nx, int64_t ny, int64_t nz, float threshold, const int32_t* voff,
+                     const int32_t* toff, const float* lo, const float* hi, float* vertices, float* normals,
+                     int32_t* faces, mfnerf_stream_t stream);
+
 /* ---------------------------------------------------------------- training batch */
 
 /* One training batch from GPU-resident images (datasets/base.py:22-35 + train.py:93-105 get_rays,

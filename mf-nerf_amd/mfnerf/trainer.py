@@ -236,6 +236,13 @@ class Trainer:
         return {"psnr": sum(psnrs) / len(psnrs), "ssim": sum(ssims) / len(ssims),
                 "psnr_per_view": psnrs, "ssim_per_view": ssims}
 
+    def extract_mesh(self, **kw):
+        """A triangle mesh of the current density field (test.ipynb's mesh cell): to_ngp() followed by
+        mfnerf.mesh.extract_mesh(model, **kw) -- resolution, sigma_threshold, bounds, colors, chunk,
+        return_sigma.  One host synchronisation."""
+        from .mesh import extract_mesh
+        return extract_mesh(self.to_ngp(), **kw)
+
     def refined_poses(self):
         """Every training image's refined pose (n_img,3,4) from the current dR / dT (train.py:295); the
         dataset's own poses without optimize_ext."""
