@@ -577,6 +577,55 @@ int mfnerf_mesh_emit(const float* sigma, int64_t nx, int64_t ny, int64_t nz, flo
                      const int32_t* toff, const float* lo, const float* hi, float* vertices, float* normals,
                      int32_t* faces, mfnerf_stream_t stream);
 
+/* Mesh cleaning (csrc/mesh_clean.hip; specification: tests/mesh_clean_ref.py).  The reference leaves
+ * floaters to the user (test.ipynb mesh cell: "tune these parameters until the whole object lies
+ * tightly in range with little noise", "sigma_threshold controls the noise"); these entry points
+ * remove them on the device.  Everywhere: faces (F, 3) i32 with indices in [0, V) -- a face with an
+ * index outside that range is skipped by every kernel (it joins nothing, counts nowhere and is never
+ * kept), so bad input cannot write out of bounds; 0 <= V, F < 2^31; V == 0 or F == 0 launches
+ * nothing and leaves every output untouched.  Integer atomics only: each output is a pure function
+ * of the inputs, the same bits on every run.
+ *
+ * mfnerf_mesh_components replaces the "little noise" tuning of the test.ipynb mesh cell by an exact
+ * notion of a floater: two vertices are connected when a face holds both; labels (V) i32 = the
+ * smallest vertex index of each vertex's component (a vertex in no face labels itself);
+ * face_counts (V) i32 = at r the number of faces of the component labelled r, 0 at every other
+ * index.  Lock-free union-find in labels, then a flatten and a count launch; no host read. */
+int mfnerf_mesh_components(const int32_t* faces, int64_t V, int64_t F, int32_t* labels, int32_t* face_counts,
+                           mfnerf_stream_t stream);
+/* test.ipynb mesh cell ("little noise"), the choice of what stays: with max_count the largest face
+ * count, the component labelled r is kept when count[r] > 0, count[r] >= min_faces and
+ * (double)count[r] >= (double)min_fraction * (double)max_count (min_fraction in [0, 1], an fp32 value
+ * widened); with largest_only != 0 only the component of the largest count, the smallest label among
+ * equals.  labels and face_counts as mfnerf_mesh_components wrote them.  Writes vkeep (V) u8 and
+ * fkeep (F) u8, 1 = kept (a face is kept with its component), and stats, DEVICE int64[3]:
+ * [0] components, [1] components kept, [2] scratch.  The thresholds are computed on the device. */
+int mfnerf_mesh_select(const int32_t* faces, int64_t V, int64_t F, const int32_t* labels, const int32_t* face_counts,
+                       int64_t min_faces, float min_fraction, int64_t largest_only, uint8_t* vkeep, uint8_t* fkeep,
+                       int64_t* stats, mfnerf_stream_t stream);
+/* test.ipynb mesh cell ("little noise"), the cleaned mesh: a stable compaction.  voff (V) / foff (F)
+ * i32 are the EXCLUSIVE prefix sums of vkeep / fkeep.  Kept vertex v goes to row voff[v] of
+ * out_vertices / out_normals / out_colors ((V', 3) f32, copied bit for bit; colors and out_colors may
+ * both be NULL), kept face f to row foff[f] of out_faces (F', 3) i32 with each index i replaced by
+ * voff[i].  Precondition: flags from mfnerf_mesh_select on the same mesh (every vertex of a kept
+ * face is kept).  The caller sizes the outputs from the scans' totals V' and F'. */
+int mfnerf_mesh_compact(const float* vertices, const float* normals, const float* colors, const int32_t* faces,
+                        int64_t V, int64_t F, const uint8_t* vkeep, const int32_t* voff, const uint8_t* fkeep,
+                        const int32_t* foff, float* out_vertices, float* out_normals, float* out_colors,
+                        int32_t* out_faces, mfnerf_stream_t stream);
+/* test.ipynb mesh cell ("tune these parameters until the whole object lies tightly in range"): the
+ * density lattice culled by the occupancy bitfield, in place.  sigma (nx*ny*nz) f32 on the lattice
+ * of the mesh section above (lo, hi HOST arrays of 3 floats; the fp32 positions
+ * lo + i*((hi - lo)/(n - 1)) of mfnerf_mesh_lattice_points).  A point with any |coordinate| > scale is
+ * cleared; otherwise mip = the position's cascade (raymarching.cu:19-23), its cell that of the march
+ * (raymarching.cu:205-220 without the dt term: there is no ray), and the point is cleared when bit
+ * (mip*G^3 + morton) & 7 of byte (mip*G^3 + morton) >> 3 of bitfield (mfnerf_packbits' layout) is
+ * clear.  Cleared means sigma = 0.0f, a finite value; other points keep their bits.  G = grid_size
+ * must be a power of two <= 1024, cascades in [1, 32], bitfield_bytes >= cascades*G^3/8. */
+int mfnerf_mesh_occupancy_mask(float* sigma, const float* lo, const float* hi, int64_t nx, int64_t ny, int64_t nz,
+                               const uint8_t* bitfield, int64_t bitfield_bytes, int64_t cascades, int64_t grid_size,
+                               float scale, mfnerf_stream_t stream);
+
 /* ---------------------------------------------------------------- training batch */
 
 /* One training batch from GPU-resident images (datasets/base.py:22-35 + train.py:93-105 get_rays,

@@ -72,6 +72,10 @@ SIGNATURES = {
     "mfnerf_mesh_lattice_points": (_I, [_P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P]),
     "mfnerf_mesh_count": (_I, [_P, _I64, _I64, _I64, _F, _P, _P, _P]),
     "mfnerf_mesh_emit": (_I, [_P, _I64, _I64, _I64, _F, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mfnerf_mesh_components": (_I, [_P, _I64, _I64, _P, _P, _P]),
+    "mfnerf_mesh_select": (_I, [_P, _I64, _I64, _P, _P, _I64, _F, _I64, _P, _P, _P, _P]),
+    "mfnerf_mesh_compact": (_I, [_P, _P, _P, _P, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mfnerf_mesh_occupancy_mask": (_I, [_P, _P, _P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _F, _P]),
     "mfnerf_distortion_loss_fw": (_I, [_P, _P, _P, _P, _I64, _I64, _P, _P, _P, _P]),
     "mfnerf_distortion_loss_bw": (_I, [_P, _P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P]),
     "mfnerf_nerf_loss": (_I, [_P, _P, _P, _I64, _I64, _F, _F, _F, _F, _P, _P, _P, _P]),

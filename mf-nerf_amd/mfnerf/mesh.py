@@ -10,6 +10,10 @@ csrc/mesh.hip (marching tetrahedra on the Kuhn split: the same iso-surface as ma
 triangulated differently, watertight without an ambiguity table; specification: tests/mesh_ref.py).
 Everything stays on the device; the vertex and face totals are read back once to size the outputs:
 ONE host synchronisation per mesh.
+
+Floaters (csrc/mesh_clean.hip; specification: tests/mesh_clean_ref.py): extract_mesh(occupancy=True)
+clears the lattice where the renderer never samples, and clean_mesh / extract_mesh(clean={...})
+removes small connected components, with one more synchronisation to size the cleaned mesh.
 """
 import ctypes
 
@@ -127,10 +131,11 @@ def _resolution3(resolution):
 
 
 @torch.no_grad()
-def density_lattice(model, resolution, lo, hi, chunk=1 << 22):
+def density_lattice(model, resolution, lo, hi, chunk=1 << 22, occupancy=False):
     """model.density on the lattice of `resolution` cells spanning [lo, hi] -> sigma (nz, ny, nx) f32.
     Slab by slab (mfnerf_mesh_lattice_points -> grid encode -> field_fw density_only) through two
-    chunk-sized buffers, with no host synchronisation; the values do not depend on `chunk`."""
+    chunk-sized buffers, with no host synchronisation; the values do not depend on `chunk`.
+    occupancy=True then clears (occupancy_mask) the points the renderer never samples."""
     from . import field
     Rx, Ry, Rz = _resolution3(resolution)
     nx, ny, nz = Rx + 1, Ry + 1, Rz + 1
@@ -147,7 +152,27 @@ def density_lattice(model, resolution, lo, hi, chunk=1 << 22):
         call("mfnerf_mesh_lattice_points", lo3, hi3, nx, ny, nz, first, cnt, ptr(xyz), stream())
         field.grid_encode_fw(xyz, cnt, table16, model.layout, model.desc, model._x_min, model._x_range, out=feat)
         field.field_fw(feat, None, cnt, packed, model.rgb_width, density_only=True, sigma=sigma[first:first + cnt])
-    return sigma.view(nz, ny, nx)
+    sigma = sigma.view(nz, ny, nx)
+    if occupancy:
+        occupancy_mask(sigma, lo, hi, model.density_bitfield, model.cascades, model.scale, model.grid_size)
+    return sigma
+
+
+def occupancy_mask(sigma, lo, hi, density_bitfield, cascades, scale, grid_size):
+    """Clear IN PLACE (mfnerf_mesh_occupancy_mask) the lattice values the renderer never samples:
+    points outside the scene box [-scale, scale]^3 and points whose cell of their own cascade has a
+    clear bit in density_bitfield (uint8, packbits' layout).  Cleared means 0.0; the other values
+    keep their bits.  The density there was never trained and may exceed any threshold."""
+    if not isinstance(density_bitfield, torch.Tensor) or density_bitfield.dtype != torch.uint8:
+        raise RuntimeError("density_bitfield must be a uint8 tensor")
+    if not density_bitfield.is_contiguous():
+        raise RuntimeError("density_bitfield must be contiguous")
+    nx, ny, nz = _check_lattice(sigma)
+    if not density_bitfield.is_cuda:
+        raise RuntimeError("density_bitfield must be a CUDA tensor")
+    call("mfnerf_mesh_occupancy_mask", ptr(sigma), _f3(lo, "lo"), _f3(hi, "hi"), nx, ny, nz, ptr(density_bitfield),
+         density_bitfield.numel(), int(cascades), int(grid_size), float(scale), stream())
+    return sigma
 
 
 @torch.no_grad()
@@ -164,7 +189,7 @@ def vertex_colors(model, mesh):
 
 @torch.no_grad()
 def extract_mesh(model, resolution=256, sigma_threshold=20.0, bounds=None, colors=True, chunk=1 << 22,
-                 return_sigma=False):
+                 return_sigma=False, occupancy=False, clean=None):
     """The surface sigma = sigma_threshold of an mfnerf.networks.NGP as a triangle mesh (test.ipynb's
     mesh cell, whose threshold of 20 is the default).
 
@@ -174,15 +199,148 @@ def extract_mesh(model, resolution=256, sigma_threshold=20.0, bounds=None, color
     extracts the surface with ONE host synchronisation (reading the vertex and face totals).
 
     Returns {"vertices", "normals", "faces"} as mesh_from_lattice; colors=True adds "colors" (V,3) f32 =
-    model(vertices, -normals)'s rgb; return_sigma=True adds "sigma" (nz, ny, nx) f32."""
+    model(vertices, -normals)'s rgb; return_sigma=True adds "sigma" (nz, ny, nx) f32.
+
+    occupancy=True culls the lattice by the model's own occupancy bitfield first (occupancy_mask: the
+    density was never trained where the renderer does not sample); it needs sigma_threshold > 0, since
+    a cleared point holds 0.  clean = a dict of clean_mesh's keyword arguments removes small
+    components (one more host synchronisation) and adds "components"; colours are computed afterwards,
+    on the kept vertices only.  With both at their defaults nothing changes."""
+    if occupancy and not sigma_threshold > 0:
+        raise RuntimeError(f"occupancy=True needs sigma_threshold > 0 (got {sigma_threshold}): a culled lattice "
+                           "point holds 0.0 and would lie inside the surface")
+    if clean is not None:
+        clean = dict(clean)
+        _check_selection(**clean)
     lo, hi = (-float(model.scale), float(model.scale)) if bounds is None else bounds
-    sigma = density_lattice(model, resolution, lo, hi, chunk)
+    sigma = density_lattice(model, resolution, lo, hi, chunk, occupancy)
     mesh = mesh_from_lattice(sigma, sigma_threshold, lo, hi)
+    if clean is not None:
+        mesh = clean_mesh(mesh, **clean)
     if colors:
         mesh["colors"] = vertex_colors(model, mesh)
     if return_sigma:
         mesh["sigma"] = sigma
     return mesh
+
+
+# ------------------------------------------------------------------------------- cleaning
+def _check_mesh(mesh):
+    """(V, F) of a mesh dict after the argument checks; touches no device."""
+    if not isinstance(mesh, dict) or any(k not in mesh for k in ("vertices", "normals", "faces")):
+        raise RuntimeError('mesh must be a dict with "vertices", "normals" and "faces"')
+    names = [("vertices", torch.float32), ("normals", torch.float32), ("faces", torch.int32)]
+    if mesh.get("colors") is not None:
+        names.append(("colors", torch.float32))
+    for name, dtype in names:
+        t = mesh[name]
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != 3:
+            raise RuntimeError(f"{name} must be a (n, 3) tensor")
+        if t.dtype != dtype:
+            raise RuntimeError(f"{name} must be {dtype}, got {t.dtype}")
+        if not t.is_contiguous():
+            raise RuntimeError(f"{name} must be contiguous")
+    V, F = mesh["vertices"].shape[0], mesh["faces"].shape[0]
+    for name, _ in names:
+        if name != "faces" and mesh[name].shape[0] != V:
+            raise RuntimeError(f"{name} must have one row per vertex ({V}), got {mesh[name].shape[0]}")
+    if V >= _LIMIT or F >= _LIMIT:
+        raise RuntimeError(f"the mesh must have fewer than 2^31 vertices and faces (got {V} and {F})")
+    for name, _ in names:
+        if not mesh[name].is_cuda:
+            raise RuntimeError(f"{name} must be a CUDA tensor")
+    return V, F
+
+
+def _check_selection(min_faces=0, min_fraction=0.0, largest_only=False):
+    if int(min_faces) != min_faces or min_faces < 0:
+        raise RuntimeError(f"min_faces must be an integer >= 0, got {min_faces}")
+    if not 0.0 <= float(min_fraction) <= 1.0:
+        raise RuntimeError(f"min_fraction must lie in [0, 1], got {min_fraction}")
+
+
+def _components(faces, V):
+    F = faces.shape[0]
+    if V == 0 or F == 0:  # every vertex its own component, no launch of ours
+        return (torch.arange(V, dtype=torch.int32, device=faces.device),
+                torch.zeros(V, dtype=torch.int32, device=faces.device))
+    labels = torch.empty(V, dtype=torch.int32, device=faces.device)
+    face_counts = torch.empty(V, dtype=torch.int32, device=faces.device)
+    call("mfnerf_mesh_components", ptr(faces), V, F, ptr(labels), ptr(face_counts), stream())
+    return labels, face_counts
+
+
+@torch.no_grad()
+def components(mesh):
+    """Connected components of a mesh (mfnerf_mesh_components): two vertices are connected when a face
+    holds both.  Returns {"labels" (V,) i32: the smallest vertex index of each vertex's component,
+    "face_counts" (V,) i32: at index r the faces of the component labelled r, 0 elsewhere}, device
+    tensors, no host read; the same bits on every run.  Precondition: face indices in [0, V) (a face
+    with an index outside is ignored: it connects nothing and counts nowhere)."""
+    V, _ = _check_mesh(mesh)
+    labels, face_counts = _components(mesh["faces"], V)
+    return {"labels": labels, "face_counts": face_counts}
+
+
+@torch.no_grad()
+def clean_mesh(mesh, min_faces=0, min_fraction=0.0, largest_only=False):
+    """A copy of `mesh` without its floaters.  A component (see `components`) is kept when its face
+    count is >= min_faces and >= min_fraction (rounded to fp32) times the largest component's, the
+    product and the comparison in fp64; largest_only keeps the largest alone, the one with the smallest
+    label among equals.  A vertex no face uses is always dropped, and so is a face with an index
+    outside [0, V) (indices in [0, V) are the precondition).
+
+    The compaction is stable: kept vertices and faces keep their order, "vertices", "normals" and
+    "colors" (if given) are copied bit for bit, face indices are renumbered.  Returns a new dict with
+    those keys, "components": (total, kept) as ints and "sigma" passed through if present; the input
+    is not modified.  Selection thresholds are computed on the device; ONE host synchronisation reads
+    [V', F', total, kept] to size the outputs.  An empty mesh comes back empty without a launch."""
+    _check_selection(min_faces, min_fraction, largest_only)
+    V, F = _check_mesh(mesh)
+    if V == 0 or F == 0:  # nothing is referenced: every vertex is a component of no face
+        return compact(mesh, None, (0, 0, V, 0))
+    labels, face_counts = _components(mesh["faces"], V)
+    flags, sizes = select_and_scan(mesh, labels, face_counts, min_faces, min_fraction, largest_only)
+    del labels, face_counts
+    return compact(mesh, flags, sizes)
+
+
+def select_and_scan(mesh, labels, face_counts, min_faces=0, min_fraction=0.0, largest_only=False):
+    """clean_mesh's middle (mfnerf_mesh_select, two scans, the read): ((vkeep (V,) u8, voff (V,) i32,
+    fkeep (F,) u8, foff (F,) i32), (V', F', components, components kept)).  V, F > 0."""
+    V, F = mesh["vertices"].shape[0], mesh["faces"].shape[0]
+    dev = mesh["vertices"].device
+    vkeep = torch.empty(V, dtype=torch.uint8, device=dev)
+    fkeep = torch.empty(F, dtype=torch.uint8, device=dev)
+    stats = torch.empty(3, dtype=torch.int64, device=dev)
+    call("mfnerf_mesh_select", ptr(mesh["faces"]), V, F, ptr(labels), ptr(face_counts), int(min_faces),
+         float(min_fraction), int(bool(largest_only)), ptr(vkeep), ptr(fkeep), ptr(stats), stream())
+    voff, Vk = _exclusive_scan(vkeep)
+    foff, Fk = _exclusive_scan(fkeep)
+    sizes = tuple(int(v) for v in torch.stack([Vk, Fk, stats[0], stats[1]]).cpu())  # the one read
+    return (vkeep, voff, fkeep, foff), sizes
+
+
+def compact(mesh, flags, sizes):
+    """clean_mesh's end (mfnerf_mesh_compact) into freshly sized outputs; F' == 0 makes no launch."""
+    Vk, Fk, total, kept = sizes
+    if Vk >= _LIMIT or Fk >= _LIMIT:
+        raise RuntimeError(f"the mesh must have fewer than 2^31 vertices and faces (got {Vk} and {Fk})")
+    dev = mesh["vertices"].device
+    has_colors = mesh.get("colors") is not None
+    out = {k: torch.empty(Vk, 3, dtype=torch.float32, device=dev)
+           for k in ["vertices", "normals"] + (["colors"] if has_colors else [])}
+    out["faces"] = torch.empty(Fk, 3, dtype=torch.int32, device=dev)
+    out["components"] = (total, kept)
+    if "sigma" in mesh:
+        out["sigma"] = mesh["sigma"]
+    if Fk > 0:  # a kept face brings three kept vertices
+        vkeep, voff, fkeep, foff = flags
+        call("mfnerf_mesh_compact", ptr(mesh["vertices"]), ptr(mesh["normals"]),
+             ptr(mesh["colors"] if has_colors else None), ptr(mesh["faces"]), mesh["vertices"].shape[0],
+             mesh["faces"].shape[0], ptr(vkeep), ptr(voff), ptr(fkeep), ptr(foff), ptr(out["vertices"]),
+             ptr(out["normals"]), ptr(out["colors"] if has_colors else None), ptr(out["faces"]), stream())
+    return out
 
 
 def save_ply(path, mesh):

@@ -239,7 +239,7 @@ class Trainer:
     def extract_mesh(self, **kw):
         """A triangle mesh of the current density field (test.ipynb's mesh cell): to_ngp() followed by
         mfnerf.mesh.extract_mesh(model, **kw) -- resolution, sigma_threshold, bounds, colors, chunk,
-        return_sigma.  One host synchronisation."""
+        return_sigma, occupancy, clean.  One host synchronisation, one more with `clean`."""
         from .mesh import extract_mesh
         return extract_mesh(self.to_ngp(), **kw)
 
