@@ -464,6 +464,34 @@ int mfnerf_mlp_bw(const void* x_f16, int64_t n, const void* packed, int n_in, in
                   int output_sigmoid, const void* dout_f16, float* dx, float* grad, void* workspace,
                   mfnerf_stream_t stream);
 
+/* ---------------------------------------------------------------- HDR tonemappers (exposure path)
+ * The reference's --use_exposure model (networks.py:81-94,111-132): rgb_net's output is log-radiance,
+ * and one tcnn.Network(1, 1, FullyFusedMLP ReLU/Sigmoid, 64 neurons, 1 hidden layer) per colour
+ * channel maps log-radiance + log(exposure) to an LDR value.  params (C, 2048) f32: per channel
+ * W1 (64,16) row-major, then W2 (16,64) row-major -- tcnn's layout with the scalar input padded to
+ * 16, the padding holding ones (so b_j = sum_{k>=1} W1[j,k] is unit j's bias).  Per sample, channel:
+ *     x16 = half(float(lograd) + log e),  h_j = half(relu(W1h[j,0]*x16 + b_j)),
+ *     y = half(sigmoid(sum_j W2h[0,j]*h_j)),  weights rounded to half, fp32 accumulation
+ * ("Tonemapper semantics").  C = 1 (one network: tcnn.Network.forward) or 3 (the
+ * model's three in one launch); no padded (n,16) row exists in memory.
+ * exposure: NULL = unit exposure (log e = 0); else device f32 read at [i * exposure_stride],
+ * exposure_stride 0 (one value for all samples: the test path's scalar, train.py:102-103) or
+ * 1 (per sample: the train path's repeat_interleave, rendering.py:142-144). */
+
+/* networks.py:81-94,111-132 forward: lograd (n,C) f16 -> rgb (n,C) f16.  n = 0 is a no-op. */
+int mfnerf_tonemap_fw(const void* lograd_f16, const float* exposure, int64_t exposure_stride, int64_t n, int C,
+                      const float* params, void* rgb_f16, mfnerf_stream_t stream);
+/* networks.py:81-94,111-132 backward workspace: one row of C*192 f32 sums per workgroup (any content). */
+int64_t mfnerf_tonemap_bw_workspace(int64_t n, int C);
+/* networks.py:81-94,111-132 backward, fp32 from the forward's fp16 points, no loss scale:
+ * dz = dL_drgb*y*(1-y) from the saved rgb_f16, h_j recomputed and gated on h_j > 0.  Writes
+ * dL_dlograd (n,C) f32 and OVERWRITES grad_params (C,2048) f32 (dW1 columns 1..15 all hold the bias
+ * gradient, dW2 rows 1..15 are zero; n = 0 zeroes it).  No gradient to the exposure.  Per-workgroup
+ * partial sums, then a second launch adds them in a fixed order: no atomics, the same bits every run. */
+int mfnerf_tonemap_bw(const void* lograd_f16, const float* exposure, int64_t exposure_stride, int64_t n, int C,
+                      const float* params, const void* rgb_f16, const float* dL_drgb, float* dL_dlograd,
+                      float* grad_params, void* workspace, mfnerf_stream_t stream);
+
 
 /* ---------------------------------------------------------------- occupancy grid refresh */
 

@@ -143,6 +143,9 @@ SIGNATURES = {
     "mfnerf_mlp_fw": (_I, [_P, _I64, _P, _I, _I, _I, _I, _I, _P, _P]),
     "mfnerf_mlp_bw_workspace": (_I64, [_I64, _I, _I, _I, _I]),
     "mfnerf_mlp_bw": (_I, [_P, _I64, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "mfnerf_tonemap_fw": (_I, [_P, _P, _I64, _I64, _I, _P, _P, _P]),
+    "mfnerf_tonemap_bw_workspace": (_I64, [_I64, _I]),
+    "mfnerf_tonemap_bw": (_I, [_P, _P, _I64, _I64, _I, _P, _P, _P, _P, _P, _P, _P]),
     "mfnerf_check_finite": (_I, [_P, _I64, _P, _P]),
     "mfnerf_flag_to_shards": (_I, [_P, _I64, _I64, _P, _P]),
     "mfnerf_flag_from_shard": (_I, [_P, _P, _P]),

@@ -212,6 +212,10 @@ def extract_mesh(model, resolution=256, sigma_threshold=20.0, bounds=None, color
     if clean is not None:
         clean = dict(clean)
         _check_selection(**clean)
+    if colors and getattr(model, "rgb_act", "Sigmoid") != "Sigmoid":
+        raise NotImplementedError("extract_mesh(colors=True): vertex colours of an HDR/exposure model "
+                                  "(rgb_act='None') need an exposure, which this call does not take; pass "
+                                  "colors=False")
     lo, hi = (-float(model.scale), float(model.scale)) if bounds is None else bounds
     sigma = density_lattice(model, resolution, lo, hi, chunk, occupancy)
     mesh = mesh_from_lattice(sigma, sigma_threshold, lo, hi)

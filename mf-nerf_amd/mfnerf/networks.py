@@ -6,7 +6,15 @@ registers on the model), parameters (xyz_encoder.params, rgb_net.params in tcnn 
 methods (density, forward, get_all_cells, sample_uniform_and_occupied_cells,
 mark_invisible_cells, update_density_grid).  forward/density run the fused field kernels
 (grid encode -> MFMA MLPs -> TruncExp/SH4/sigmoid) instead of three tcnn modules.
-The HDR path (rgb_act='None', tonemappers) is out of scope.
+
+The HDR/exposure model (rgb_act='None', train.py:73 with --use_exposure; networks.py:81-94,111-155)
+adds the three tonemapper_net_{i} modules (2048 parameters each, the reference's state-dict keys) and
+log_radiance_to_rgb.  Its forward takes the module route -- xyz_encoder, TruncExp, dir_encoder,
+rgb_net with no output activation, since the fused field kernels bake the sigmoid in -- and then one
+tonemap launch for the three channels (mfnerf.tonemap), or TruncExp of the log-radiance with
+output_radiance.  density and the occupancy methods run the fused kernels for either model.  The
+single-launch test renderer, mesh colours and the fused training step serve the Sigmoid model only
+and refuse an HDR model.
 """
 import numpy as np
 import torch
@@ -14,8 +22,10 @@ from einops import rearrange
 from torch import nn
 
 from . import tcnn, vren
+from .custom_functions import TruncExp
 from .field import NGPDensityFunction, NGPFieldFunction
 from .rendering import NEAR_DISTANCE
+from .tonemap import TonemapFunction
 
 
 def _meshgrid3d(G, device=None):
@@ -59,8 +69,8 @@ def mark_invisible_cells(density_grid, grid_coords, scale, K, poses, img_wh, chu
 class NGP(nn.Module):
     def __init__(self, scale, hparams, rgb_act="Sigmoid"):
         super().__init__()
-        if rgb_act != "Sigmoid":
-            raise NotImplementedError("the HDR/exposure path (rgb_act='None') is out of scope")
+        if rgb_act not in ("Sigmoid", "None"):
+            raise NotImplementedError(f"rgb_act={rgb_act!r}: the reference builds 'Sigmoid' or 'None' (train.py:73)")
         self.rgb_act = rgb_act
         self.scale = scale
         self.register_buffer("center", torch.zeros(1, 3))
@@ -97,6 +107,12 @@ class NGP(nn.Module):
             n_input_dims=32, n_output_dims=3,
             network_config={"otype": "FullyFusedMLP", "activation": "ReLU", "output_activation": self.rgb_act,
                             "n_neurons": hparams.rgb_channels, "n_hidden_layers": hparams.rgb_layers})
+        if self.rgb_act == "None":  # rgb_net's output is log-radiance: one tonemapper per colour (networks.py:81-94)
+            for i in range(3):
+                setattr(self, f"tonemapper_net_{i}", tcnn.Network(
+                    n_input_dims=1, n_output_dims=1,
+                    network_config={"otype": "FullyFusedMLP", "activation": "ReLU", "output_activation": "Sigmoid",
+                                    "n_neurons": 64, "n_hidden_layers": 1}))
         self.layout, self.desc = self.xyz_encoder.layout, self.xyz_encoder.desc
         s = np.float32(scale)
         self._x_min = float(-s)
@@ -109,8 +125,32 @@ class NGP(nn.Module):
         return NGPDensityFunction.apply(x, self.xyz_encoder.params, self.rgb_net.params, self.layout, self.desc,
                                         self._x_min, self._x_range, self.rgb_width)
 
+    def log_radiance_to_rgb(self, log_radiances, **kwargs):
+        """networks.py:111-132 (rgb_act='None' only): log-radiance (N,3) -> rgb (N,3) f16 through the
+        three tonemappers in one mfnerf_tonemap_fw call; kwargs['exposure'] per sample, one value or
+        absent (unit exposure)."""
+        if self.rgb_act != "None":
+            raise RuntimeError("log_radiance_to_rgb: this model has no tonemappers (rgb_act='Sigmoid')")
+        params = torch.cat([getattr(self, f"tonemapper_net_{i}").params for i in range(3)])
+        return TonemapFunction.apply(log_radiances, kwargs.get("exposure"), params)
+
+    def _forward_hdr(self, x, d, **kwargs):
+        """networks.py:134-155 with rgb_act='None', module by module as the reference runs it (the fused
+        field kernels bake the sigmoid in): rgb_net returns log-radiance, which becomes radiance
+        (output_radiance) or, through the tonemappers, rgb at the given exposure."""
+        h = self.xyz_encoder((x - self.xyz_min) / (self.xyz_max - self.xyz_min))
+        sigmas = TruncExp.apply(h[:, 0])
+        d = d / torch.norm(d, dim=1, keepdim=True)
+        d = self.dir_encoder((d + 1) / 2)
+        rgbs = self.rgb_net(torch.cat([d, h], 1))
+        if kwargs.get("output_radiance", False):
+            return sigmas, TruncExp.apply(rgbs)
+        return sigmas, self.log_radiance_to_rgb(rgbs, **kwargs)
+
     def forward(self, x, d, **kwargs):
         """networks.py:134-155 -> sigmas (N) f32, rgbs (N,3)."""
+        if self.rgb_act == "None":
+            return self._forward_hdr(x, d, **kwargs)
         return NGPFieldFunction.apply(x, d, self.xyz_encoder.params, self.rgb_net.params, self.layout, self.desc,
                                       self._x_min, self._x_range, self.rgb_width)
 

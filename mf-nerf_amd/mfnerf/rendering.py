@@ -109,6 +109,9 @@ def render_fused(model, rays_o, rays_d, **kwargs):
     samples.sum() (the loop also counts those marched past a ray's termination inside a chunk)."""
     from . import field
     from ._lib import call, check_input, ptr, stream
+    if getattr(model, "rgb_act", "Sigmoid") != "Sigmoid":
+        raise NotImplementedError("render_fused: the single-launch renderer's field head applies the sigmoid; an "
+                                  "HDR/exposure model (rgb_act='None') renders with render(test_time=True)")
     rays_o = rays_o.contiguous()
     rays_d = rays_d.contiguous()
     check_input("rays_o", rays_o, torch.float32)

@@ -2,11 +2,16 @@
 
 Each module owns one flat fp32 `params` Parameter in tcnn's layout (state-dict keys
 `xyz_encoder.params`, `rgb_net.params` as in the reference), initialised like tcnn (grid
-U(-1e-4, 1e-4), MLP Xavier-uniform).  NGP (mfnerf.networks) does not call these forwards: it
-runs the fused gfx950 field kernels on the same parameters.  The standalone forwards are what the
+U(-1e-4, 1e-4), MLP Xavier-uniform).  The Sigmoid NGP (mfnerf.networks) does not call these forwards:
+it runs the fused gfx950 field kernels on the same parameters (the HDR model, rgb_act='None', does
+call them: the fused kernels apply the sigmoid).  The standalone forwards are what the
 reference's own networks.py runs with `sys.modules["tinycudann"] = mfnerf.tcnn`:
 grids run the HIP grid kernels, the networks the MFMA FullyFusedMLP kernels of mlp.hip
 (mfnerf_mlp_fw / _bw), with tcnn's torch-binding loss scale (128) around the fp16 backward.
+The one other network the reference builds is the HDR path's tonemapper (networks.py:81-94:
+Network(1, 1, ReLU/Sigmoid, 64 neurons, 1 hidden layer), 2048 parameters with the scalar input padded
+to 16): its forward runs the tonemap kernels (mfnerf.tonemap, one channel, unit exposure), so the
+reference's log_radiance_to_rgb works over the swap.  Any other input width than 32 still raises.
 There is no CPU path: a module on a CPU tensor raises.
 """
 import math
@@ -28,8 +33,11 @@ def _pad16(n):
 
 
 def mlp_shapes(n_in, n_out, n_neurons, n_hidden_layers):
-    """FullyFusedMLP weights, bias-free, output width padded to 16: [(out, in), ...]."""
-    shapes = [(n_neurons, n_in)] + [(n_neurons, n_neurons)] * (n_hidden_layers - 1)
+    """FullyFusedMLP weights, bias-free, input and output widths padded to 16: [(out, in), ...].
+    (tcnn pads the input with its identity encoding, which fills the padding with ones: a scalar
+    input becomes the row [x, 1, ..., 1], and Network(1, 1, 64 neurons, 1 hidden layer) owns
+    64*16 + 16*64 = 2048 parameters.)"""
+    shapes = [(n_neurons, _pad16(n_in))] + [(n_neurons, n_neurons)] * (n_hidden_layers - 1)
     return shapes + [(_pad16(n_out), n_neurons)]
 
 
@@ -186,7 +194,15 @@ class Network(torch.nn.Module):
         g = torch.Generator().manual_seed(seed)
         self.params = torch.nn.Parameter(_xavier(self.shapes, g))
 
+    def is_tonemapper(self):
+        """The reference's tonemapper_net_{i} configuration (networks.py:83-93)."""
+        return (self.n_input_dims, self.n_output_dims, self.width, self.depth, self.activation,
+                self.output_activation) == (1, 1, 64, 1, "ReLU", "Sigmoid")
+
     def forward(self, x):
+        if self.is_tonemapper():  # (n, 1) -> (n, 1) f16 on the tonemap kernels, one channel, unit exposure
+            from .tonemap import TonemapFunction
+            return TonemapFunction.apply(x, None, self.params)
         return mlp_forward(x, self.params, self.width, self.depth, self.n_output_dims, self.activation,
                            self.output_activation)
 

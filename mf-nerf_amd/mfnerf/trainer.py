@@ -62,6 +62,7 @@ class HParams:
     steps_per_epoch: int = 1000  # len(train dataset) (datasets/base.py:17-20)
     optimize_ext: bool = False   # camera-pose refinement (opt.py:47, train.py:91-94, 122-139)
     pose_lr: float = 1e-6        # train.py:139 hard-codes it
+    use_exposure: bool = False   # the HDR-NeRF setting (opt.py, train.py:73,102-103,172-177)
 
 
 def cosine_lr(epoch, hp: HParams):
@@ -80,6 +81,9 @@ class Trainer:
     def __init__(self, hp: HParams, train, device="cuda", rank=0, world=1, graphs=True):
         if hp.rgb_layers != 2:
             raise NotImplementedError("the fused field head implements rgb_layers=2")
+        if getattr(hp, "use_exposure", False):
+            raise NotImplementedError("use_exposure: the fused training step's field kernels apply the sigmoid; the "
+                                      "HDR/exposure model (NGP(rgb_act='None')) trains through rendering.render()")
         if hp.optimize_ext and world > 1:
             raise NotImplementedError("optimize_ext (pose refinement) runs on one GPU: the per-image offsets are "
                                       "not exchanged between ranks")
