@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from conftest import ROOT
+from field_ref import fp32_autograd as _fp32_autograd
 from mfnerf import field as FLD
 from mfnerf._lib import call, load, ptr, stream
 from mfnerf.grid import GridLayout
@@ -432,25 +433,13 @@ def test_field_width_unsupported(gpu):
         FLD.pack_field_weights(torch.zeros(3072, device=gpu), torch.zeros(FLD.rgb_net_params(96), device=gpu), 96)
 
 
-def _fp32_autograd(feat, dirs, px, pr, dsig, drgb, width=64):
-    f32 = feat.float().requires_grad_(True)
-    a = px.half().float().requires_grad_(True)
-    b = pr.half().float().requires_grad_(True)
-    W = width
-    W1 = a[:2048].view(64, 32); W2 = a[2048:3072].view(16, 64)
-    R1 = b[:W * 32].view(W, 32); R2 = b[W * 32:W * 32 + W * W].view(W, W); R3 = b[W * 32 + W * W:].view(16, W)
-    y1 = torch.relu(f32 @ W1.t()); h = y1 @ W2.t()
-    sigma = torch.exp(h[:, 0])
-    dn = dirs / torch.norm(dirs, dim=1, keepdim=True)
-    r1 = torch.relu(torch.cat([FO.sh4((dn + 1) / 2), h], 1) @ R1.t()); r2 = torch.relu(r1 @ R2.t())
-    c = torch.sigmoid(r2 @ R3.t())[:, :3]
-    ((sigma * dsig).sum() + (c * drgb).sum()).backward()
-    return f32.grad, a.grad, b.grad
-
-
 @pytest.mark.parametrize("wscale,sig_on,width", [(1.0, 0.0, 64), (1.0, 1.0, 64), (3.0, 1.0, 64), (1.0, 1.0, 128),
                                                  (3.0, 1.0, 128)])
 def test_field_bw(gpu, wscale, sig_on, width):
+    """The one-pass case: N = 3000 is 24 groups of 128 samples for the cooperative backward's 512 | 256
+    persistent workgroups, so no workgroup takes a second group and most take none.  The group loop's
+    second and third trips, exact multiples of the grid, the live count, level_l1 and the training
+    step's argument combination are tests/test_gpu_field_seams.py's."""
     N = 3000
     feat, dirs, px, pr = _field_inputs(N, seed=5, wscale=wscale, width=width)
     g = torch.Generator().manual_seed(6)
