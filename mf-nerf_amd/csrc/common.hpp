@@ -17,11 +17,6 @@ namespace mfn {
 __device__ __forceinline__ float clampf(float f, float a, float b) { return fmaxf(a, fminf(f, b)); }
 __device__ __forceinline__ float signf(float x) { return copysignf(1.0f, x); }
 
-// raymarching.cu:11-13
-__device__ __forceinline__ float calc_dt(float t, float exp_step_factor, int max_samples, int grid_size, float scale) {
-    return clampf(t * exp_step_factor, MFN_SQRT3 / (float)max_samples, MFN_SQRT3 * 2 * scale / (float)grid_size);
-}
-
 // raymarching.cu:19-23 -- frexpf exponent of the largest |coordinate|
 __device__ __forceinline__ int mip_from_pos(float x, float y, float z, int cascades) {
     const float mx = fmaxf(fabsf(x), fmaxf(fabsf(y), fabsf(z)));
@@ -53,34 +48,6 @@ __host__ __device__ __forceinline__ uint32_t morton3_invert(uint32_t x) {
     x = (x | (x >> 8)) & 0xff0000ffu;
     x = (x | (x >> 16)) & 0x0000ffffu;
     return x;
-}
-
-// One occupancy lookup (raymarching.cu:205-220).  Returns the occupancy bit and the cell.
-struct Cell { int nx, ny, nz; float mip_bound; bool occ; };
-
-__device__ __forceinline__ Cell lookup_cell(float x, float y, float z, float dt, int cascades, int grid_size,
-                                            float scale, const uint8_t* __restrict__ bitfield) {
-    const uint32_t g3 = (uint32_t)grid_size * grid_size * grid_size;
-    const int mip = max(mip_from_pos(x, y, z, cascades), mip_from_dt(dt, grid_size, cascades));
-    Cell c;
-    c.mip_bound = fminf(scalbnf(1.0f, mip - 1), scale);
-    const float inv = 1 / c.mip_bound;
-    const float gs = (float)grid_size, gm1 = (float)grid_size - 1.0f;
-    c.nx = (int)clampf(0.5f * fmaf(x, inv, 1.0f) * gs, 0.0f, gm1);
-    c.ny = (int)clampf(0.5f * fmaf(y, inv, 1.0f) * gs, 0.0f, gm1);
-    c.nz = (int)clampf(0.5f * fmaf(z, inv, 1.0f) * gs, 0.0f, gm1);
-    const uint32_t idx = (uint32_t)mip * g3 + morton3((uint32_t)c.nx, (uint32_t)c.ny, (uint32_t)c.nz);
-    c.occ = (bitfield[idx >> 3] >> (idx & 7)) & 1u;
-    return c;
-}
-
-// DDA skip target (raymarching.cu:225-229)
-__device__ __forceinline__ float skip_target(float t, const Cell& c, float x, float y, float z, float dx, float dy,
-                                             float dz, float dxi, float dyi, float dzi, float gsi) {
-    const float tx = fmaf(fmaf(fmaf(0.5f, signf(dx), (float)c.nx + 0.5f) * gsi, 2.0f, -1.0f), c.mip_bound, -x) * dxi;
-    const float ty = fmaf(fmaf(fmaf(0.5f, signf(dy), (float)c.ny + 0.5f) * gsi, 2.0f, -1.0f), c.mip_bound, -y) * dyi;
-    const float tz = fmaf(fmaf(fmaf(0.5f, signf(dz), (float)c.nz + 0.5f) * gsi, 2.0f, -1.0f), c.mip_bound, -z) * dzi;
-    return t + fmaxf(0.0f, fminf(tx, fminf(ty, tz)));
 }
 
 __device__ __forceinline__ float fast_exp(float x) { return __expf(x); }

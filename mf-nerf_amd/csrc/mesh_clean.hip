@@ -286,7 +286,7 @@ struct MaskLattice {
 };
 
 // One thread per lattice point, x fastest (as lattice_points_kernel of mesh.hip, whose fp32
-// position expression this repeats).  The cell is lookup_cell's (common.hpp) with the position's
+// position expression this repeats).  The cell is lookup_cell's (ray_march.hpp) with the position's
 // mip alone: there is no ray here, hence no dt term.
 __global__ __launch_bounds__(CLEAN_BLOCK) void occupancy_mask_kernel(float* __restrict__ sigma, MaskLattice L,
                                                                     int64_t n,

@@ -16,7 +16,8 @@
 // only), so its outputs do not depend on the lane, the wave or the rest of the batch.
 #include <cmath>
 
-#include "common.hpp"
+#include "ray_march.hpp"
+#include "composite_sample.hpp"
 #include "grid_geo.hpp"
 #include "field_fwd.hpp"
 #include "../../include/mfnerf.h"
@@ -67,12 +68,14 @@ void render_test_kernel(const RenderParams p, const mfnerf_grid_desc D) {
     const int lane = threadIdx.x & 63;
     const int r = lane & 31, h = lane >> 5;
     const uint32_t below = (1u << r) - 1u;
-    const float gsi = 1.0f / (float)p.grid_size;
-    const float qscale = (float)p.cascades;  // the reference's quirk: cascades passed as `scale`
+    const MarchGrid g = test_grid(p);
     const float cx = p.center[0], cy = p.center[1], cz = p.center[2];
     const float hx = p.half_size[0], hy = p.half_size[1], hz = p.half_size[2];
 
-    // the pair's ray (identical on both lanes) and, on lanes h == 0, its compositing sums
+    // the pair's ray (identical on both lanes) and, on lanes h == 0, its compositing sums.  They live
+    // across trips as plain floats and are handed to the shared functions as a Ray / RaySums made on
+    // the spot: as struct members the compiler carries them through the loops in another order, and
+    // this kernel's register allocation (three waves, 9 spills) follows that order
     bool have = false;
     int32_t ray = 0, n = 0;
     float ox = 0.f, oy = 0.f, oz = 0.f, dx = 0.f, dy = 0.f, dz = 0.f, dxi = 0.f, dyi = 0.f, dzi = 0.f;
@@ -99,24 +102,18 @@ void render_test_kernel(const RenderParams p, const mfnerf_grid_desc D) {
         float sx = 0.f, sy = 0.f, sz = 0.f, sdt = 0.f, st = 0.f;
         for (;;) {
             if (have && !ready) {
-                // march_test_kernel's step; the skip loop also stops at t2, past which the ray ends
-                // whatever t is (same samples, and no trip count that depends on a far skip target)
+                // the test-time march step; the skip also stops at t2, past which the ray ends whatever
+                // t is (same samples, and no trip count that depends on a far skip target)
+                const Ray ry{ox, oy, oz, dx, dy, dz, dxi, dyi, dzi};
                 while (t < t2) {
-                    const float x = fmaf(t, dx, ox), y = fmaf(t, dy, oy), z = fmaf(t, dz, oz);
-                    const float dt = calc_dt(t, p.exp_step, p.max_samples, p.grid_size, qscale);
-                    const Cell c = lookup_cell(x, y, z, dt, p.cascades, p.grid_size, p.scale, p.bitfield);
-                    if (c.occ) {
-                        sx = x; sy = y; sz = z; sdt = dt; st = t;
-                        t += dt;
+                    const MarchPoint m = march_point(g, ry, t);
+                    if (m.c.occ) {
+                        sx = m.x; sy = m.y; sz = m.z; sdt = m.dt; st = t;
+                        t += m.dt;
                         ready = true;
                         break;
                     }
-                    const float tt = skip_target(t, c, x, y, z, dx, dy, dz, dxi, dyi, dzi, gsi);
-                    do {
-                        const float tp = t;
-                        t += calc_dt(t, p.exp_step, p.max_samples, p.grid_size, qscale);
-                        if (t == tp) t = t2;  // a step below t's resolution (a degenerate ray): end it
-                    } while (t < tt && t < t2);
+                    t = skip_empty_to(g, ry, m, t, t2);
                 }
                 if (!ready) finish();  // left the box
             }
@@ -131,16 +128,14 @@ void render_test_kernel(const RenderParams p, const mfnerf_grid_desc D) {
             if (need) {
                 const int32_t idx = base + (int)__popc(m & below);
                 if (idx < p.n_rays) {
-                    // the slab test of ray_aabb_kernel for one box, then the near clamp of rendering.py:28
                     ray = idx;
-                    ox = p.o[3 * (int64_t)idx]; oy = p.o[3 * (int64_t)idx + 1]; oz = p.o[3 * (int64_t)idx + 2];
-                    dx = p.d[3 * (int64_t)idx]; dy = p.d[3 * (int64_t)idx + 1]; dz = p.d[3 * (int64_t)idx + 2];
-                    dxi = 1.0f / dx; dyi = 1.0f / dy; dzi = 1.0f / dz;
-                    const float tminx = (cx - hx - ox) * dxi, tminy = (cy - hy - oy) * dyi, tminz = (cz - hz - oz) * dzi;
-                    const float tmaxx = (cx + hx - ox) * dxi, tmaxy = (cy + hy - oy) * dyi, tmaxz = (cz + hz - oz) * dzi;
-                    float t1 = fmaxf(fmaxf(fminf(tminx, tmaxx), fminf(tminy, tmaxy)), fminf(tminz, tmaxz));
-                    float te = fminf(fminf(fmaxf(tminx, tmaxx), fmaxf(tminy, tmaxy)), fmaxf(tminz, tmaxz));
-                    if (t1 > te) { t1 = -1.0f; te = -1.0f; }
+                    const Ray ry = load_ray(p.o, p.d, (int64_t)idx);
+                    ox = ry.ox; oy = ry.oy; oz = ry.oz;
+                    dx = ry.dx; dy = ry.dy; dz = ry.dz;
+                    dxi = ry.dxi; dyi = ry.dyi; dzi = ry.dzi;
+                    float t1, te;
+                    slab_test(ry, cx, cy, cz, hx, hy, hz, t1, te);
+                    // an exit behind the origin is a miss, as in ray_aabb_kernel; the near clamp of rendering.py:28
                     if (te > 0) t1 = fmaxf(t1, 0.0f);
                     else { t1 = -1.0f; te = -1.0f; }
                     if (t1 >= 0 && t1 < NEAR_DISTANCE) t1 = NEAR_DISTANCE;
@@ -200,18 +195,14 @@ void render_test_kernel(const RenderParams p, const mfnerf_grid_desc D) {
         FwdTile<W> F;
         forward_tiles<W, false, 1, true>(lds, lane, &I, &ready, &F);
 
-        // ---- composite_test_kernel's statements on the pair's one sample
+        // ---- the pair's one sample onto its sums
         bool term = false;
         if (ready && h == 0) {
             const float sigma = __expf(F.h0);  // TruncExp forward, as field_fw_kernel stores it
             const float c0 = (float)(_Float16)F.rgb[0], c1 = (float)(_Float16)F.rgb[1], c2 = (float)(_Float16)F.rgb[2];
-            const float a = 1.0f - fast_exp(-sigma * sdt);
-            const float w = a * T;
-            R = fmaf(w, c0, R); G = fmaf(w, c1, G); B = fmaf(w, c2, B);
-            Dp = fmaf(w, st, Dp);
-            O += w;
-            T *= 1.0f - a;
-            term = T <= p.T_thr;
+            RaySums S{T, O, Dp, R, G, B};
+            term = composite_sample(S, sigma, sdt, st, c0, c1, c2, p.T_thr);
+            T = S.T; O = S.O; Dp = S.D; R = S.R; G = S.G; B = S.B;
         }
         const uint32_t tb = (uint32_t)__ballot(term);  // lanes h == 0 decide for their pairs
         if (ready) {

@@ -1,5 +1,5 @@
 """The wave-per-ray compositing kernels, the loss kernels and the march's capacity clipping at their
-seams, against the fp64 references of tests/composite_ref.py (csrc/vren_ops.hip).
+seams, against the fp64 references of tests/composite_ref.py (csrc/vren_composite.hip, csrc/vren_march.hip).
 
 The batch (composite_ref.seam_rays: 93 rays, 22 373 samples) has ray lengths around every multiple
 of the 64-sample chunk, termination designed at lane 63, lane 0 of the next chunk, the last and the

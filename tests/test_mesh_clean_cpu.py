@@ -266,7 +266,9 @@ def test_build_lists_the_new_unit():
     mk = open(os.path.join(PKG, "csrc", "Makefile")).read()
     assert re.search(r"^SRCS :=.*\bmesh_clean\.hip\b", mk, re.M)
     assert re.search(r"^resource:.*\bmesh_clean\.hip\b", mk, re.M)
-    assert re.search(r"^\t.*kernel-resource-usage -c mesh_clean\.hip\b", mk, re.M)
+    # (one rule compiles every unit of that list: the list is handed on, and the rule reports a unit)
+    assert re.search(r"^resource:.*\n\t.*\$\(\^:%\.hip=resource-%\)", mk, re.M)
+    assert re.search(r"^resource-%: %\.hip\n\t.*kernel-resource-usage -c \$<", mk, re.M)
     # the sizes the GPU tests place their edge cases around
     src = open(os.path.join(PKG, "csrc", "mesh_clean.hip")).read()
     assert re.search(r"constexpr int CLEAN_BLOCK = 256;", src) and re.search(r"constexpr int ITEMS = 16;", src)
