@@ -67,6 +67,8 @@ def _mlp_packed(params, cfg):
         return hit[1]
     n_in, width, depth, n_out = cfg
     nb = load().mfnerf_mlp_packed_bytes(n_in, width, depth, n_out)
+    if nb < 0:  # a network the kernels are not instantiated for: the library's message names it
+        raise RuntimeError("mfnerf.tcnn: " + load().mfnerf_last_error().decode(errors="replace"))
     blob = torch.empty(nb // 2, dtype=torch.float16, device=params.device)
     call("mfnerf_mlp_pack", ptr(params.detach().float().contiguous()), n_in, width, depth, n_out, ptr(blob), stream())
     if len(_packed) > 8:

@@ -41,7 +41,8 @@ def mlp16(x, params, shapes, n_out, out_act):
     return h[:, :n_out]
 
 
-CFGS = [(64, 1, 16, "None"), (64, 2, 3, "Sigmoid"), (128, 2, 3, "Sigmoid"), (128, 1, 16, "None")]
+CFGS = [(64, 1, 16, "None"), (64, 2, 3, "Sigmoid"), (128, 2, 3, "Sigmoid"), (128, 1, 16, "None"),
+        (64, 2, 3, "None"), (128, 2, 3, "None")]
 
 
 @pytest.mark.parametrize("width,depth,n_out,out_act", CFGS)
