@@ -367,6 +367,13 @@ int mfnerf_field_pack_weights_f16(const void* params_xyz_f16, const void* params
  * dirs (n,3) f32 (ignored when density_only) -> sigma (n) f32, rgb (n,3) f32. */
 int mfnerf_field_fw(const void* feat_f16, int64_t feat_plane_stride, const float* dirs, int64_t n, const int32_t* n_dev, const void* packed,
                     int rgb_width, int density_only, float* sigma, float* rgb, mfnerf_stream_t stream);
+/* mfnerf_field_fw for the HDR model (NGP(rgb_act='None'), networks.py:134-155): the rgb head has no
+ * output activation.  sigma as mfnerf_field_fw writes it (the same code up to the epilogue);
+ * lograd_f16 (n,3) f16 = the head's three outputs rounded to half (tcnn's fp16 output), the input
+ * format of the tonemap kernels.  Rows below min(n, *n_dev) are written. */
+int mfnerf_field_fw_lograd(const void* feat_f16, int64_t feat_plane_stride, const float* dirs, int64_t n,
+                           const int32_t* n_dev, const void* packed, int rgb_width, float* sigma, void* lograd_f16,
+                           mfnerf_stream_t stream);
 /* The occupancy refresh's density query (networks.py:252-259, `density_grid_tmp[c, indices] =
  * self.density(xyzs)`): mfnerf_field_fw density_only over min(n, *n_dev) points, each sigma also
  * written to tmp[cell_idx[i]] (skipped for cell_idx < 0) -- the update's scatter in the same launch
@@ -430,6 +437,19 @@ int mfnerf_field_bw_inputs(const void* feat_f16, int64_t feat_plane_stride, cons
                            float* grad_xyz, float* grad_rgb, void* workspace, mfnerf_amp_state* amp, float* level_l1,
                            float* dL_ddirs, mfnerf_stream_t stream);
 
+/* mfnerf_field_bw / mfnerf_field_bw_inputs for the head without its sigmoid (mfnerf_field_fw_lograd):
+ * dL_dlograd (n,3) f32 is the unscaled gradient with respect to the log-radiance, so the head's
+ * output gradient is half(dL_dlograd * S) with no y(1-y) factor.  Everything else -- loss scale,
+ * n_dev, slab and deferred fold, level_l1, the non-finite flag -- is mfnerf_field_bw's. */
+int mfnerf_field_bw_lograd(const void* feat_f16, int64_t feat_plane_stride, const float* dirs, int64_t n, const int32_t* n_dev, const void* packed,
+                           int rgb_width, const float* dL_dsigma, const float* dL_dlograd, float grad_scale, float* dL_dfeat,
+                           float* grad_xyz, float* grad_rgb, void* workspace, mfnerf_amp_state* amp, float* level_l1,
+                           mfnerf_stream_t stream);
+int mfnerf_field_bw_inputs_lograd(const void* feat_f16, int64_t feat_plane_stride, const float* dirs, int64_t n, const int32_t* n_dev, const void* packed,
+                                  int rgb_width, const float* dL_dsigma, const float* dL_dlograd, float grad_scale, float* dL_dfeat,
+                                  float* grad_xyz, float* grad_rgb, void* workspace, mfnerf_amp_state* amp, float* level_l1,
+                                  float* dL_ddirs, mfnerf_stream_t stream);
+
 /* grad_xyz = grad_rgb = NULL in mfnerf_field_bw defers the weight-gradient fold: the per-block
  * partial sums stay in workspace (dL_dfeat, level_l1 and the data-gradient part of the non-finite
  * flag are complete when field_bw returns) and this call adds them into grad_xyz / grad_rgb in the
@@ -491,6 +511,38 @@ int64_t mfnerf_tonemap_bw_workspace(int64_t n, int C);
 int mfnerf_tonemap_bw(const void* lograd_f16, const float* exposure, int64_t exposure_stride, int64_t n, int C,
                       const float* params, const void* rgb_f16, const float* dL_drgb, float* dL_dlograd,
                       float* grad_params, void* workspace, mfnerf_stream_t stream);
+
+/* The pair as the fused training step runs it (C = 3): `cap` is a capacity that sizes the grid and
+ * the workspace (mfnerf_tonemap_bw_workspace(cap, 3)); the live count is min(cap, *n_dev), read on the
+ * device, and nothing past it is read or written.  rgb (cap,3) is f32 holding the half value (what
+ * the compositing kernels read; mfnerf_field_fw's convention): the forward's output equals
+ * mfnerf_tonemap_fw's converted to float, bit for bit, and dL_dlograd equals mfnerf_tonemap_bw's.
+ * grad_params keeps the backward's properties (fixed-order sums, no atomics, workspace content
+ * free, *n_dev == 0 zeroes it); its summation order is that of a `cap`-sized launch. */
+int mfnerf_tonemap_fw_live(const void* lograd_f16, const float* exposure, int64_t exposure_stride, int64_t cap,
+                           const int32_t* n_dev, const float* params, float* rgb, mfnerf_stream_t stream);
+int mfnerf_tonemap_bw_live(const void* lograd_f16, const float* exposure, int64_t exposure_stride, int64_t cap,
+                           const int32_t* n_dev, const float* params, const float* rgb, const float* dL_drgb,
+                           float* dL_dlograd, float* grad_params, void* workspace, mfnerf_stream_t stream);
+/* rendering.py:142-145 (exposure repeated per sample through rays_a): for every row r of rays_a
+ * (n_rays,3) i64 = (ray, start, count), exposure_s[start .. start+count) = exposure_ray[ray], clipped
+ * to min(cap, *n_dev) rows.  exposure_ray (n_rays) f32, exposure_s (cap) f32: the exposure, not its log. */
+int mfnerf_expand_exposure(const float* exposure_ray, const int64_t* rays_a, int64_t n_rays, int64_t cap,
+                           const int32_t* n_dev, float* exposure_s, mfnerf_stream_t stream);
+/* train.py:172-177: the tonemappers at log-radiance 0 and unit exposure give y_c; the loss term is
+ * mean_c 0.5 (y_c - unit_exposure_rgb)^2.  loss_out[c] (C f32) is STORED channel c's share, and the
+ * gradient (dL/dy_c = (y_c - u)/C, through the backward's fp16 points) is ADDED to grad_params
+ * (C,2048): run it after mfnerf_tonemap_bw*, which overwrites that gradient.  Deterministic.  amp
+ * (optional): amp->nonfinite is raised when the summed gradient holds an inf/nan. */
+int mfnerf_tonemap_unit_loss(const float* params, int C, float unit_exposure_rgb, float* grad_params, float* loss_out,
+                             mfnerf_amp_state* amp, mfnerf_stream_t stream);
+/* Adam for a small parameter group kept outside the flat parameter vector (the tonemappers), after
+ * mfnerf_pose_step: one workgroup, n <= 2^20, its own device step counter (bumped by an update),
+ * lr_dev (optional) overriding lr.  amp->nonfinite set: nothing is touched -- the flag is left for
+ * the main optimizer call, which does the GradScaler bookkeeping and clears it. */
+int mfnerf_side_adam_step(float* params, const float* grads, float* m, float* v, int64_t n, float lr, float beta1,
+                          float beta2, float eps, int32_t* step_dev, const float* lr_dev, const mfnerf_amp_state* amp,
+                          mfnerf_stream_t stream);
 
 
 /* ---------------------------------------------------------------- occupancy grid refresh */

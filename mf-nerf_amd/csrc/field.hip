@@ -142,7 +142,9 @@ __device__ __forceinline__ void load_tile_in(const _Float16* __restrict__ feat, 
     }
 }
 
-template <int W, bool DENSITY_ONLY>
+// LOGRAD (mfnerf_field_fw_lograd): the rgb head without its sigmoid; `rgb` then points to an (n,3) f16
+// buffer, the log-radiance as tcnn returns it (the tonemap kernels' input)
+template <int W, bool DENSITY_ONLY, bool LOGRAD = false>
 __global__ __launch_bounds__(FIELD_BLOCK) void field_fw_kernel(const _Float16* __restrict__ feat,
                                                                 int64_t plane_stride,
                                                                 const float* __restrict__ dirs, int64_t n,
@@ -173,7 +175,7 @@ __global__ __launch_bounds__(FIELD_BLOCK) void field_fw_kernel(const _Float16* _
             load_tile_in(feat, plane_stride, dirs, s, valid[q], h, !DENSITY_ONLY, I[q]);
         }
         FwdTile<W> T[P];
-        forward_tiles<W, DENSITY_ONLY, P, true>(lds, lane, I, valid, T);
+        forward_tiles<W, DENSITY_ONLY, P, true, LOGRAD>(lds, lane, I, valid, T);
 #pragma unroll
         for (int q = 0; q < P; ++q) {
             const int64_t s = (tile + q * stride) * 32 + r;
@@ -184,7 +186,12 @@ __global__ __launch_bounds__(FIELD_BLOCK) void field_fw_kernel(const _Float16* _
                     const int32_t k = cell[s];
                     if (k >= 0) cell_out[k] = sg;
                 }
-                if (!DENSITY_ONLY) {
+                if constexpr (LOGRAD) {
+                    _Float16* lograd = reinterpret_cast<_Float16*>(rgb);
+                    lograd[3 * s] = (_Float16)T[q].rgb[0];
+                    lograd[3 * s + 1] = (_Float16)T[q].rgb[1];
+                    lograd[3 * s + 2] = (_Float16)T[q].rgb[2];
+                } else if (!DENSITY_ONLY) {
                     // tcnn returns fp16 rgb; the reference casts it to fp32 for compositing
                     rgb[3 * s] = (float)(_Float16)T[q].rgb[0];
                     rgb[3 * s + 1] = (float)(_Float16)T[q].rgb[1];
@@ -355,7 +362,8 @@ struct CoopGeo {
     static_assert(W != 128 || LDS <= 160 * 1024, "one cooperative W = 128 workgroup per CU");
 };
 
-template <int W, bool PLANAR, bool DDIRS>
+// LOGRAD (mfnerf_field_bw*_lograd): dL_drgb is dL/dlograd of the head without its sigmoid
+template <int W, bool PLANAR, bool DDIRS, bool LOGRAD = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CoopGeo<W>::WAVES_PER_SIMD))) void field_bw_coop_kernel(
     const _Float16* __restrict__ feat, int64_t plane_stride, const float* __restrict__ dirs, int64_t n,
     const int32_t* __restrict__ n_dev, const _Float16* __restrict__ packed, const float* __restrict__ dL_dsigma,
@@ -437,13 +445,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CoopGeo<W>:
         fetch(4 * (g + (int64_t)gridDim.x) + wid, nx);  // (clamped past the end)
         const bool valid = tile * 32 + r < nn;
         FwdTile<W> T;
-        forward_tiles<W, false, 1>(lds, lane, &in.I, &valid, &T);
+        forward_tiles<W, false, 1, false, LOGRAD>(lds, lane, &in.I, &valid, &T);
         half8 dOb;
         {
             f32x16 dO = z;
-            dO[0] = in.g0 * S * T.rgb[0] * (1.0f - T.rgb[0]);
-            dO[1] = in.g1 * S * T.rgb[1] * (1.0f - T.rgb[1]);
-            dO[2] = in.g2 * S * T.rgb[2] * (1.0f - T.rgb[2]);
+            if constexpr (LOGRAD) {
+                dO[0] = in.g0 * S;
+                dO[1] = in.g1 * S;
+                dO[2] = in.g2 * S;
+            } else {
+                dO[0] = in.g0 * S * T.rgb[0] * (1.0f - T.rgb[0]);
+                dO[1] = in.g1 * S * T.rgb[1] * (1.0f - T.rgb[1]);
+                dO[2] = in.g2 * S * T.rgb[2] * (1.0f - T.rgb[2]);
+            }
             dOb = pack8<0, false>(dO);
         }
         //    dR2 = Wr3^T dO, masked by R2 > 0
@@ -766,7 +780,7 @@ void launch_pack(const TP* px, const TP* pr, void* packed, mfnerf_stream_t strea
                        (_Float16*)packed);
 }
 
-template <int W>
+template <int W, bool LOGRAD = false>
 void launch_fw(const void* feat, int64_t ps, const float* dirs, int64_t n, const int32_t* n_dev, const void* packed,
                int density_only, float* sigma, float* rgb, mfnerf_stream_t stream, const int32_t* cell = nullptr,
                float* cell_out = nullptr) {
@@ -778,7 +792,7 @@ void launch_fw(const void* feat, int64_t ps, const float* dirs, int64_t n, const
                            (const _Float16*)feat, ps, dirs, n, n_dev, (const _Float16*)packed, sigma, rgb, cell,
                            cell_out);
     else
-        hipLaunchKernelGGL((field_fw_kernel<W, false>), dim3(blocks), dim3(FIELD_BLOCK),
+        hipLaunchKernelGGL((field_fw_kernel<W, false, LOGRAD>), dim3(blocks), dim3(FIELD_BLOCK),
                            (size_t)Geo<W>::N_FW * FRAG_HALFS * 2, stream, (const _Float16*)feat, ps, dirs, n, n_dev,
                            (const _Float16*)packed, sigma, rgb, nullptr, nullptr);
 }
@@ -787,12 +801,12 @@ void launch_fw(const void* feat, int64_t ps, const float* dirs, int64_t n, const
 // from CoopGeo), then the slab fold (unless deferred: grad_xyz null, mfnerf_field_bw_reduce folds
 // the slab later)
 // DDIRS (mfnerf_field_bw_inputs): the kernels' direction-gradient instantiation, writing dL_ddirs
-template <int W, bool DDIRS>
+template <int W, bool DDIRS, bool LOGRAD>
 int launch_bw(const void* feat, int64_t ps, const float* dirs, int64_t n, const int32_t* n_dev, const void* packed,
               const float* dL_dsigma, const float* dL_drgb, float grad_scale, const float* scale_dev, float* dL_dfeat,
               float* grad_xyz, float* grad_rgb, void* workspace, int32_t* nonfinite, float* level_l1,
               mfnerf_stream_t stream, float* dL_ddirs) {
-    constexpr auto k0 = field_bw_coop_kernel<W, false, DDIRS>, k1 = field_bw_coop_kernel<W, true, DDIRS>;
+    constexpr auto k0 = field_bw_coop_kernel<W, false, DDIRS, LOGRAD>, k1 = field_bw_coop_kernel<W, true, DDIRS, LOGRAD>;
     constexpr size_t lds = CoopGeo<W>::LDS;
     constexpr int rows = CoopGeo<W>::BLOCKS;
     static const hipError_t attr = [] {
@@ -815,8 +829,9 @@ int launch_bw(const void* feat, int64_t ps, const float* dirs, int64_t n, const 
     return MFN_OK;
 }
 
-// mfnerf_field_bw (DDIRS off) and mfnerf_field_bw_inputs (on): the same checks and launches
-template <bool DDIRS>
+// mfnerf_field_bw (DDIRS off) and mfnerf_field_bw_inputs (on), and their _lograd forms: the same
+// checks and launches
+template <bool DDIRS, bool LOGRAD = false>
 int field_bw_impl(const void* feat_f16, int64_t feat_plane_stride, const float* dirs, int64_t n, const int32_t* n_dev,
                   const void* packed, int rgb_width, const float* dL_dsigma, const float* dL_drgb, float grad_scale,
                   float* dL_dfeat, float* grad_xyz, float* grad_rgb, void* workspace, mfnerf_amp_state* amp,
@@ -834,7 +849,7 @@ int field_bw_impl(const void* feat_f16, int64_t feat_plane_stride, const float* 
     int32_t* nonfinite = amp ? &amp->nonfinite : nullptr;
     const float* scale_dev = grad_scale == 0.0f ? &amp->scale : nullptr;
     const int st = width_dispatch(rgb_width, [&](auto w) {
-        return launch_bw<decltype(w)::value, DDIRS>(feat_f16, feat_plane_stride, dirs, n, n_dev, packed, dL_dsigma,
+        return launch_bw<decltype(w)::value, DDIRS, LOGRAD>(feat_f16, feat_plane_stride, dirs, n, n_dev, packed, dL_dsigma,
                                                     dL_drgb, grad_scale, scale_dev, dL_dfeat, grad_xyz, grad_rgb,
                                                     workspace, nonfinite, level_l1, stream, dL_ddirs);
     });
@@ -892,6 +907,22 @@ int mfnerf_field_fw(const void* feat_f16, int64_t feat_plane_stride, const float
     return mfn_check_launch("field_fw");
 }
 
+int mfnerf_field_fw_lograd(const void* feat_f16, int64_t feat_plane_stride, const float* dirs, int64_t n,
+                           const int32_t* n_dev, const void* packed, int rgb_width, float* sigma, void* lograd_f16,
+                           mfnerf_stream_t stream) {
+    if (!width_ok(rgb_width)) return bad_width(rgb_width);
+    if (n < 0 || (feat_plane_stride != 0 && feat_plane_stride < n)) { mfn_set_error("field_fw_lograd: bad size"); return MFN_ERR_INVALID; }
+    if (n == 0) return MFN_OK;
+    if (!feat_f16 || !packed || !sigma || !dirs || !lograd_f16) {
+        mfn_set_error("field_fw_lograd: null pointer"); return MFN_ERR_INVALID;
+    }
+    width_dispatch(rgb_width, [&](auto w) {
+        launch_fw<decltype(w)::value, true>(feat_f16, feat_plane_stride, dirs, n, n_dev, packed, 0, sigma,
+                                            reinterpret_cast<float*>(lograd_f16), stream);
+    });
+    return mfn_check_launch("field_fw_lograd");
+}
+
 int mfnerf_field_fw_density_scatter(const void* feat_f16, int64_t feat_plane_stride, int64_t n, const int32_t* n_dev,
                                     const void* packed, int rgb_width, float* sigma, const int32_t* cell_idx,
                                     float* tmp, mfnerf_stream_t stream) {
@@ -941,6 +972,26 @@ int mfnerf_field_bw_inputs(const void* feat_f16, int64_t feat_plane_stride, cons
                            float* dL_ddirs, mfnerf_stream_t stream) {
     return field_bw_impl<true>(feat_f16, feat_plane_stride, dirs, n, n_dev, packed, rgb_width, dL_dsigma, dL_drgb,
                                grad_scale, dL_dfeat, grad_xyz, grad_rgb, workspace, amp, level_l1, stream, dL_ddirs);
+}
+
+int mfnerf_field_bw_lograd(const void* feat_f16, int64_t feat_plane_stride, const float* dirs, int64_t n,
+                           const int32_t* n_dev, const void* packed,
+                           int rgb_width, const float* dL_dsigma, const float* dL_dlograd, float grad_scale, float* dL_dfeat,
+                           float* grad_xyz, float* grad_rgb, void* workspace, mfnerf_amp_state* amp, float* level_l1,
+                           mfnerf_stream_t stream) {
+    return field_bw_impl<false, true>(feat_f16, feat_plane_stride, dirs, n, n_dev, packed, rgb_width, dL_dsigma,
+                                      dL_dlograd, grad_scale, dL_dfeat, grad_xyz, grad_rgb, workspace, amp, level_l1,
+                                      stream, nullptr);
+}
+
+int mfnerf_field_bw_inputs_lograd(const void* feat_f16, int64_t feat_plane_stride, const float* dirs, int64_t n,
+                                  const int32_t* n_dev, const void* packed,
+                                  int rgb_width, const float* dL_dsigma, const float* dL_dlograd, float grad_scale,
+                                  float* dL_dfeat, float* grad_xyz, float* grad_rgb, void* workspace, mfnerf_amp_state* amp,
+                                  float* level_l1, float* dL_ddirs, mfnerf_stream_t stream) {
+    return field_bw_impl<true, true>(feat_f16, feat_plane_stride, dirs, n, n_dev, packed, rgb_width, dL_dsigma,
+                                     dL_dlograd, grad_scale, dL_dfeat, grad_xyz, grad_rgb, workspace, amp, level_l1,
+                                     stream, dL_ddirs);
 }
 
 static int field_bw_fold(int rgb_width, const void* workspace, float* grad_xyz, float* grad_rgb, int32_t* nonfinite,

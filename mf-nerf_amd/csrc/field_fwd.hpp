@@ -56,7 +56,7 @@ struct FwdTile {
     half8 r1[W / 32][2];
     half8 r2[W / 32][2];
     float h0;               // h[0] (f16-rounded) on lanes h==0
-    float rgb[3];           // sigmoid outputs on lanes h==0 (fp32)
+    float rgb[3];           // sigmoid outputs on lanes h==0 (fp32); LOGRAD: the layer's raw outputs
 };
 
 // Loads of one tile's inputs (feature row halves for this lane, direction), used directly or as
@@ -69,7 +69,9 @@ struct TileIn {
 // The forward of P independent tiles, stage by stage: each layer's MFMAs for every tile, then the
 // next layer.  The scheduler keeps this source order at one wave per SIMD, so a tile's packing
 // (VALU) overlaps the next tile's MFMAs, and one fragment read from LDS serves all P tiles.
-template <int W, bool DENSITY_ONLY, int P, bool ONE_TILE_FRAGS = false>
+// LOGRAD: the rgb head has no output activation (NGP(rgb_act='None'), networks.py:134-155): T.rgb is
+// the last layer's fp32 accumulator, the log-radiance before tcnn's fp16 rounding.
+template <int W, bool DENSITY_ONLY, int P, bool ONE_TILE_FRAGS = false, bool LOGRAD = false>
 __device__ __forceinline__ void forward_tiles(const _Float16* lds, int lane, const TileIn* I, const bool* valid,
                                               FwdTile<W>* T) {
     using G = Geo<W>;
@@ -181,7 +183,10 @@ __device__ __forceinline__ void forward_tiles(const _Float16* lds, int lane, con
 #pragma unroll
     for (int q = 0; q < P; ++q)
 #pragma unroll
-        for (int c = 0; c < 3; ++c) T[q].rgb[c] = 1.0f / (1.0f + __expf(-o[q][c]));
+        for (int c = 0; c < 3; ++c) {
+            if constexpr (LOGRAD) T[q].rgb[c] = o[q][c];
+            else T[q].rgb[c] = 1.0f / (1.0f + __expf(-o[q][c]));
+        }
 }
 
 __device__ __forceinline__ void load_frags(_Float16* lds, const _Float16* __restrict__ packed, int n_frags) {

@@ -146,6 +146,15 @@ SIGNATURES = {
     "mfnerf_tonemap_fw": (_I, [_P, _P, _I64, _I64, _I, _P, _P, _P]),
     "mfnerf_tonemap_bw_workspace": (_I64, [_I64, _I]),
     "mfnerf_tonemap_bw": (_I, [_P, _P, _I64, _I64, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "mfnerf_tonemap_fw_live": (_I, [_P, _P, _I64, _I64, _P, _P, _P, _P]),
+    "mfnerf_tonemap_bw_live": (_I, [_P, _P, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mfnerf_expand_exposure": (_I, [_P, _P, _I64, _I64, _P, _P, _P]),
+    "mfnerf_tonemap_unit_loss": (_I, [_P, _I, _F, _P, _P, _P, _P]),
+    "mfnerf_side_adam_step": (_I, [_P, _P, _P, _P, _I64, _F, _F, _F, _F, _P, _P, _P, _P]),
+    "mfnerf_field_fw_lograd": (_I, [_P, _I64, _P, _I64, _P, _P, _I, _P, _P, _P]),
+    "mfnerf_field_bw_lograd": (_I, [_P, _I64, _P, _I64, _P, _P, _I, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P]),
+    "mfnerf_field_bw_inputs_lograd": (_I, [_P, _I64, _P, _I64, _P, _P, _I, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P,
+                                           _P]),
     "mfnerf_check_finite": (_I, [_P, _I64, _P, _P]),
     "mfnerf_flag_to_shards": (_I, [_P, _I64, _I64, _P, _P]),
     "mfnerf_flag_from_shard": (_I, [_P, _P, _P]),

@@ -281,10 +281,13 @@ class ColmapDataset:
 class DeviceDataset:
     """Images (n_img, hw, 3), poses (n_img, 3, 4) and camera directions (hw, 3) resident in HBM;
     sample(out) draws one training batch into a (3, N, 3) buffer with one launch (graph-safe: the
-    draw counter lives on the device).  strategy: 'all_images' or 'same_image' (base.py:25-28)."""
+    draw counter lives on the device).  strategy: 'all_images' or 'same_image' (base.py:25-28).
+    exposure (n_img,) f32: one exposure per image (the HDR-NeRF setting, datasets/base.py:34-35,
+    colmap.py:134-154: a ray's exposure is its image's), with unit_exposure_rgb, the dataset's target
+    of the unit-exposure loss term (train.py:172-177: 0.73 synthetic, 0.5 real); None without them."""
 
     def __init__(self, images, poses, directions, K=None, img_wh=None, device="cuda", seed=0,
-                 strategy="all_images"):
+                 strategy="all_images", exposure=None, unit_exposure_rgb=None):
         self.images = images.float().contiguous().to(device)
         self.poses = poses.float().contiguous().to(device)
         self.directions = directions.float().contiguous().to(device)
@@ -294,10 +297,20 @@ class DeviceDataset:
         self.seed = int(seed)
         self.same_image = {"all_images": 0, "same_image": 1}[strategy]
         self.calls = torch.zeros(2, dtype=torch.int64, device=device)  # device draw counter + its launch ticket
+        self.exposure = self.unit_exposure_rgb = None
+        if exposure is not None:
+            self.exposure = torch.as_tensor(exposure, dtype=torch.float32).reshape(-1).contiguous().to(device)
+            if self.exposure.numel() != self.n_img:
+                raise ValueError(f"exposure has {self.exposure.numel()} values for {self.n_img} images")
+            self.unit_exposure_rgb = 0.5 if unit_exposure_rgb is None else float(unit_exposure_rgb)
 
     @classmethod
     def from_dataset(cls, ds, device="cuda", **kw):
-        """From an NSVFDataset or a ColmapDataset (rays, poses, directions, K, img_wh)."""
+        """From an NSVFDataset or a ColmapDataset (rays, poses, directions, K, img_wh; and, when the
+        source carries them, its per-image exposure and unit_exposure_rgb)."""
+        for name in ("exposure", "unit_exposure_rgb"):
+            if getattr(ds, name, None) is not None:
+                kw.setdefault(name, getattr(ds, name))
         return cls(ds.rays, ds.poses, ds.directions, K=ds.K, img_wh=ds.img_wh, device=device, **kw)
 
     from_nsvf = from_dataset
@@ -364,7 +377,8 @@ class BallScene:
         sc.r = torch.from_numpy(g.uniform(radius[0], radius[1], size=n_balls)).float()
         return sc
 
-    def render(self, o, d):
+    def render(self, o, d, return_hit=False):
+        """(N,3) colours; return_hit: also the (N,) mask of rays that hit a ball."""
         o, d = o.double(), d.double()
         c, r, rgb = (t.double().to(o.device) for t in (self.c, self.r, self.rgb))
         dn = d / d.norm(dim=-1, keepdim=True)
@@ -384,7 +398,7 @@ class BallScene:
             pat = torch.sin(f * x[:, 0]) * torch.sin(f * x[:, 1]) * torch.sin(f * x[:, 2])
             out[hit] = (out[hit] + 0.3 * pat[:, None] * torch.tensor([1.0, -0.6, 0.8], dtype=out.dtype,
                                                                      device=out.device)).clamp(0, 1)
-        return out.float()
+        return (out.float(), hit) if return_hit else out.float()
 
     def density_grid(self, G=128, cascades=1):
         """Occupancy prior (density 100 inside balls, 0 elsewhere) in the reference's Morton order."""
@@ -406,3 +420,38 @@ def ball_scene_views(scene, n_views, W, focal, radius=1.5, seed=0, device="cpu")
         o, d = get_rays(dd, p.to(device))
         imgs.append(scene.render(o, d))
     return torch.stack(imgs), poses, dirs, K
+
+
+# ---------------------------------------------------------------------------- analytic HDR scene
+HDR_EXPOSURES = (0.25, 1.0, 4.0)
+UNIT_EXPOSURE_RGB_SYNTHETIC = 0.73  # train.py:172-177's target on synthetic scenes (0.5 on real ones)
+
+
+def camera_response(x):
+    """The fixed camera response of the analytic HDR scene: clip(x, 0, 1)^(1/2.2)."""
+    return x.clamp(0, 1) ** (1 / 2.2)
+
+
+def hdr_ball_scene_views(scene, n_poses, W, focal, exposures=HDR_EXPOSURES, gain=1.0, radius=1.5, seed=0,
+                         device="cpu"):
+    """The analytic scene photographed at several exposures (the HDR-NeRF setting): per pose of
+    ball_scene_views and per exposure e one image camera_response(gain * colour * e) where a ball is
+    hit -- BallScene's colours taken as radiance -- and white elsewhere (the synthetic background the
+    step blends over, at every exposure).  Returns (images (n_poses * E, W*W, 3), poses, directions,
+    K, exposure (n_poses * E,)), image i = pose i // E at exposure i % E."""
+    from . import synthetic
+    poses = synthetic.camera_poses(n_cams=n_poses, seed=seed, radius=radius)
+    K = torch.tensor([[focal, 0, W / 2], [0, focal, W / 2], [0, 0, 1]], dtype=torch.float32)
+    dirs = get_ray_directions(W, W, K)
+    dd = dirs.to(device)
+    imgs, out_poses, exps = [], [], []
+    for p in poses:
+        o, d = get_rays(dd, p.to(device))
+        rad, hit = scene.render(o, d, return_hit=True)
+        for e in exposures:
+            img = torch.ones_like(rad)
+            img[hit] = camera_response(gain * rad[hit] * e)
+            imgs.append(img)
+            out_poses.append(p)
+            exps.append(float(e))
+    return torch.stack(imgs), torch.stack(out_poses), dirs, K, torch.tensor(exps, dtype=torch.float32)

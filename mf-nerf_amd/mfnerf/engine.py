@@ -18,6 +18,9 @@ raymarching_train does); kernels that run per sample read the live count from th
 so Adam is one launch and the gradient zeroing one memset; an fp16 mirror of the whole vector is
 refreshed by the same Adam pass and is what the grid kernels gather from.
 Multi-GPU: run/replay(exchange=dp.allreduce_mean_) all-reduces `grads` between backward and Adam.
+HDR (StepConfig.hdr, the reference's --use_exposure): the field head returns log-radiance and the
+three tonemappers sit between it and the compositing, forward and backward; their parameters are a
+side group outside the flat vector with an Adam launch of their own (_tm_buffers, _tm_update).
 """
 import ctypes
 import math
@@ -98,6 +101,16 @@ class StepConfig:
     # Synthetic scenes (scale <= 0.5) ignore the flag: white, bit for bit the step without it.  Off:
     # the same launches and buffers as without the option
     random_bg: bool = False
+    # --use_exposure, the HDR-NeRF model (train.py:73,102-103,172-177; networks.py:81-94,111-155): the
+    # rgb head returns log-radiance (no sigmoid) and three tonemappers map log-radiance + log(exposure)
+    # of the ray's image to the colour that is composited; the step's loss gains the unit-exposure
+    # term 0.5 (tonemap(0, exposure 1) - unit_exposure_rgb)^2 (0.73 synthetic, 0.5 real: a property of
+    # the dataset).  The tonemappers' 3 x 2048 parameters are a side group with their own Adam
+    # (tm_params, tm_m, tm_v, tm_step_dev) sharing the field's lr, betas and eps.  Batches carry a
+    # per-ray exposure (Batch.exposure, or the attached dataset's per-image exposures).  Needs one
+    # part, no shard and no exchange.  Off: the same launches and buffers as without the option
+    hdr: bool = False
+    unit_exposure_rgb: float = 0.5
 
     def __post_init__(self):
         if self.refine_poses:
@@ -110,6 +123,7 @@ class Batch:
     rays_d: torch.Tensor
     rgb: torch.Tensor
     buf: Optional[torch.Tensor] = None  # the (3, N, 3) buffer the three are views into, if packed
+    exposure: Optional[torch.Tensor] = None  # (N,) f32 per-ray exposure (StepConfig.hdr)
 
 
 class _State:
@@ -127,10 +141,34 @@ def _packed_batch(buf):
 _nomark = lambda _name: None  # noqa: E731  (the mark= of a step nobody times)
 
 
+TM_PARAMS = 2048  # one tonemapper (tonemap.N_PARAMS): W1 (64,16), then W2 (16,64), tcnn's layout
+
+
 def init_params(c: StepConfig, n_params, n_alloc, seed):
     """The flat initial parameters [xyz MLP | rgb MLP | table] (host tensor, n_alloc long, zero
     padding): tcnn's init -- Xavier-uniform per MLP matrix, table U(-1e-4, 1e-4) -- from a seeded
     generator, so a CPU restatement of the step can start from the very same weights."""
+    return _init_draws(c, n_params, n_alloc, seed)[0]
+
+
+def init_tonemappers(c: StepConfig, n_params, n_alloc, seed):
+    """The HDR step's initial tonemapper parameters (3, 2048), host tensor: tcnn's Xavier-uniform per
+    matrix, drawn from init_params' generator AFTER its draws (the field's init is the LDR step's)."""
+    return _draw_tonemappers(_init_draws(c, n_params, n_alloc, seed)[1])
+
+
+def _draw_tonemappers(g):
+    p = torch.zeros(3, TM_PARAMS)
+    for ch in range(3):
+        off = 0
+        for o, k in [(64, 16), (16, 64)]:
+            s = math.sqrt(6.0 / (o + k))
+            p[ch, off:off + o * k].uniform_(-s, s, generator=g)
+            off += o * k
+    return p
+
+
+def _init_draws(c: StepConfig, n_params, n_alloc, seed):
     g = torch.Generator().manual_seed(seed)
     p = torch.zeros(n_alloc)
     off = 0
@@ -139,7 +177,7 @@ def init_params(c: StepConfig, n_params, n_alloc, seed):
         p[off:off + o * k].uniform_(-s, s, generator=g)
         off += o * k
     p[off:n_params].uniform_(-1e-4, 1e-4, generator=g)  # tcnn grid init
-    return p
+    return p, g
 
 
 class TrainStep:
@@ -152,6 +190,9 @@ class TrainStep:
             raise ValueError(f"n_rays={c.n_rays} must split into n_parts={c.n_parts} equal parts")
         if c.refine_poses and c.n_parts != 1:
             raise ValueError(f"refine_poses needs n_parts == 1 (got {c.n_parts}): the pose gradient is reduced "
+                             "over the whole batch in one chain")
+        if c.hdr and c.n_parts != 1:
+            raise ValueError(f"hdr needs n_parts == 1 (got {c.n_parts}): the tonemappers' gradient is reduced "
                              "over the whole batch in one chain")
         self.cascades = max(1 + int(np.ceil(np.log2(2 * c.scale))), 1)
         self.G = 128
@@ -170,7 +211,8 @@ class TrainStep:
         self.exp_step_factor, self.bg_value = (EXP_STEP_FACTOR, BG_REAL) if c.scale > 0.5 else (0.0, BG_SYNTHETIC)
 
         dev = self.dev
-        self.params = init_params(c, self.n_params, self.n_alloc, seed).to(dev)
+        p0, gen0 = _init_draws(c, self.n_params, self.n_alloc, seed)
+        self.params = p0.to(dev)
         self.grads = torch.zeros(self.n_alloc, device=dev)
         self.m = torch.zeros(self.n_alloc, device=dev)
         self.v = torch.zeros(self.n_alloc, device=dev)
@@ -186,6 +228,11 @@ class TrainStep:
         self.adam_step = 0                                            # host mirror
         self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev)  # Adam's t, bumped on the device
         self.lr_dev = torch.full((1,), float(c.lr), dtype=torch.float32, device=dev)
+        # hdr: the tonemappers, a side parameter group (_tm_buffers); absent (None) without it
+        self.tm_params = self.tm_grad = self.tm_m = self.tm_v = self.tm_step_dev = None
+        if c.hdr:
+            self._tm_buffers(_draw_tonemappers(gen0))
+        del p0, gen0
         self.graphs = None
         self.samples_marched = torch.zeros(1, dtype=torch.int64, device=dev)
 
@@ -213,8 +260,11 @@ class TrainStep:
         # compositing kernel) + 64 accumulated slots (unfused path: NeRFLoss atomics, distortion)
         self._nb_part = -(-self.Np // 4)
         self._level_l1 = torch.zeros(c.L, dtype=torch.float32, device=dev)
-        self.loss_parts = torch.zeros(c.n_parts * self._nb_part + 64, dtype=torch.float32, device=dev)
-        self._loss_acc = self.loss_parts[c.n_parts * self._nb_part:]
+        # (+ hdr: the unit-exposure term's three channel shares, stored by mfnerf_tonemap_unit_loss)
+        n_fused = c.n_parts * self._nb_part
+        self.loss_parts = torch.zeros(n_fused + 64 + (3 if c.hdr else 0), dtype=torch.float32, device=dev)
+        self._loss_acc = self.loss_parts[n_fused:n_fused + 64]
+        self._loss_unit = self.loss_parts[n_fused + 64:]
         self.state = _State()
         self._use(self.mbuf[0])
         self.gen = torch.Generator(device=dev)
@@ -264,6 +314,63 @@ class TrainStep:
         self.graphs = None
         if self.cfg.refine_poses:
             self._pose_buffers(ds)
+
+    # ---------------------------------------------------------------- HDR / exposure
+    def _tm_buffers(self, p0):
+        """The tonemappers as a side parameter group (as dR / dT are): parameters, the step's gradient,
+        Adam moments and step count, all touched on the main stream only."""
+        f32 = dict(dtype=torch.float32, device=self.dev)
+        self.tm_params = p0.to(self.dev).contiguous()
+        self.tm_grad = torch.zeros(3, TM_PARAMS, **f32)
+        self.tm_m = torch.zeros(3, TM_PARAMS, **f32)
+        self.tm_v = torch.zeros(3, TM_PARAMS, **f32)
+        self.tm_step_dev = torch.zeros(1, dtype=torch.int32, device=self.dev)
+
+    def _check_hdr(self, exchange=None):
+        if not self.cfg.hdr:
+            return
+        if self.shard is not None or exchange is not None:
+            raise ValueError("hdr does not run with a sharded optimizer or a gradient exchange: "
+                             "data-parallel HDR training is out of scope")
+        if self.dataset is not None and self.dataset.exposure is None:
+            raise ValueError("hdr needs a dataset with per-image exposures (DeviceDataset(exposure=...))")
+
+    def _stage_exposure(self, batch, mb):
+        """A passed batch's per-ray exposure into the march buffer set the batch is marched into."""
+        e = batch.exposure
+        if e is None:
+            raise ValueError("hdr: a batch the caller passes needs its per-ray exposure (Batch.exposure, (N,) f32)")
+        if e.numel() != self.cfg.n_rays:
+            raise ValueError(f"hdr: Batch.exposure has {e.numel()} values for {self.cfg.n_rays} rays")
+        mb.exposure.copy_(e.reshape(-1))
+
+    def _tonemap_fw(self, mb, q):
+        """rendering.py:142-145 + networks.py:111-132 between the field and the compositing: the rays'
+        exposures repeated per sample, then log-radiance + log(exposure) through the tonemappers into
+        rgb_s (fp32 holding the half values, what the compositing reads)."""
+        t, m, cap, s = self.parts[q], mb.part[q], self.cap_p, stream()
+        call("mfnerf_expand_exposure", ptr(mb.exposure[q * self.Np:(q + 1) * self.Np]), ptr(m.rays_a), self.Np, cap,
+             ptr(m.counter), ptr(t.exposure_s), s)
+        call("mfnerf_tonemap_fw_live", ptr(t.lograd), ptr(t.exposure_s), 1, cap, ptr(m.counter), ptr(self.tm_params),
+             ptr(t.rgb_s), s)
+
+    def _tonemap_bw(self, mb, q):
+        """dL/drgb_s -> dL/dlograd and the tonemappers' gradient (overwritten), then the unit-exposure
+        term (train.py:172-177): its loss into the step's loss slots, its gradient added on top; a
+        non-finite tonemapper gradient raises the step's flag."""
+        t, m, cap, s = self.parts[q], mb.part[q], self.cap_p, stream()
+        call("mfnerf_tonemap_bw_live", ptr(t.lograd), ptr(t.exposure_s), 1, cap, ptr(m.counter), ptr(self.tm_params),
+             ptr(t.rgb_s), ptr(t.drgb_s), ptr(t.dlograd), ptr(self.tm_grad), ptr(t.tm_ws), s)
+        call("mfnerf_tonemap_unit_loss", ptr(self.tm_params), 3, float(self.cfg.unit_exposure_rgb), ptr(self.tm_grad),
+             ptr(self._loss_unit), self._amp_ptr(), s)
+
+    def _tm_update(self):
+        """The tonemappers' Adam (train.py:131-136: the field's lr, betas and eps), after field_bw -- the
+        step's non-finite flag is final -- and before the main optimizer call, which clears it: a
+        skipped step skips both."""
+        call("mfnerf_side_adam_step", ptr(self.tm_params), ptr(self.tm_grad), ptr(self.tm_m), ptr(self.tm_v),
+             self.tm_params.numel(), float(self.cfg.lr), *ADAM_BETAS, self.cfg.eps, ptr(self.tm_step_dev),
+             ptr(self.lr_dev), self._amp_ptr(), stream())
 
     # ---------------------------------------------------------------- pose refinement
     def _pose_buffers(self, ds):
@@ -355,6 +462,11 @@ class TrainStep:
             t.ddirs = torch.empty(cap, 3, **f32)
             t.dL_drays_o = torch.zeros(Np, 3, **f32)
             t.dL_drays_d = torch.zeros(Np, 3, **f32)
+        if c.hdr:
+            t.lograd = torch.empty(cap, 3, dtype=torch.float16, device=dev)  # the head's fp16 output
+            t.exposure_s = torch.empty(cap, **f32)
+            t.dlograd = torch.empty(cap, 3, **f32)
+            t.tm_ws = torch.empty(max(16, load().mfnerf_tonemap_bw_workspace(cap, 3)) // 4, **f32)
         nb = (load().mfnerf_grid_encode_bw_binned_workspace(self.desc, self._bin_slots()) if self._binned()
               else load().mfnerf_grid_encode_bw_workspace(self.desc))
         t.grid_ws = torch.zeros(max(16, nb) // 4, **f32)
@@ -385,8 +497,10 @@ class TrainStep:
             ws_bytes = load().mfnerf_raymarching_train_workspace(self.Np, c.max_samples)
             t.march_ws = torch.empty(max(16, ws_bytes), dtype=torch.uint8, device=dev)
             m.part.append(t)
-        if c.refine_poses and self.dataset is not None:
+        if c.hdr or (c.refine_poses and self.dataset is not None):
             self._pose_idx_buffers(m)
+        if c.hdr:
+            m.exposure = torch.ones(N, **f32)  # per ray, of the batch marched into this set
         if self._random_bg():
             m.bg = torch.zeros(3, **f32)  # the colour of the batch marched into this set
         return m
@@ -478,6 +592,8 @@ class TrainStep:
         if self.cfg.refine_poses:
             raise ValueError("refine_poses does not run with a sharded optimizer: data-parallel pose refinement "
                              "is out of scope")
+        if self.cfg.hdr:
+            raise ValueError("hdr does not run with a sharded optimizer: data-parallel HDR training is out of scope")
         if self.n_alloc % (64 * world):
             raise ValueError(f"world size {world} does not divide the padded parameter count {self.n_alloc}")
         k = self.n_alloc // world
@@ -499,7 +615,11 @@ class TrainStep:
         kw = {"bg": mb.bg} if self._random_bg() else {}
         if self.cfg.refine_poses:
             kw.update(img_idx=mb.img_idx, pix_idx=mb.pix_idx, poses=self.pose_buf[self.mbuf.index(mb)])
+        if self.cfg.hdr:
+            kw.update(img_idx=mb.img_idx, pix_idx=mb.pix_idx)
         self.dataset.sample(batch.buf, prep=prep, **kw)
+        if self.cfg.hdr:  # datasets/base.py:34-35: a ray's exposure is its image's (a gather on the draw's stream)
+            torch.index_select(self.dataset.exposure, 0, mb.img_idx, out=mb.exposure)
 
     def _march(self, batch: Batch, mb, mark, prepped=False, noise=None, bg=None):
         """AABB + near clamp + noise (and, random_bg, the background colour: from the step's generator
@@ -539,9 +659,11 @@ class TrainStep:
         m = mb.part[q]
         return ptr(m.xyzs), self.cap_p, ptr(m.counter), self.x_min, self.x_range, self.desc
 
-    def _chain(self, batch: Batch, mb, q, mark):
+    def _chain(self, batch: Batch, mb, q, mark, side_adam=True):
         """Part q: encode -> field -> composite -> loss -> composite bw -> field bw (no grid bw).
-        Part 0 also zeroes the gradient (every part's writes come after it)."""
+        Part 0 also zeroes the gradient (every part's writes come after it).  hdr: the field head
+        without its sigmoid, the tonemappers between it and the compositing in both directions, the
+        unit-exposure term, and (side_adam) the tonemappers' Adam at the end."""
         c, s = self.cfg, stream()
         t, m = self.parts[q], mb.part[q]
         Np, cap = self.Np, self.cap_p
@@ -558,9 +680,16 @@ class TrainStep:
         call("mfnerf_grid_encode_fw_planar", *self._enc_args(mb, q), ptr(self.p16[self.off_table:]), ptr(t.feat),
              cap, s)
         mark("grid_fw")
-        call("mfnerf_field_fw", ptr(t.feat), cap, ptr(m.dirs), cap, ptr(m.counter), ptr(self.packed), c.rgb_width, 0,
-             ptr(t.sigma), ptr(t.rgb_s), s)
-        mark("field_fw")
+        if c.hdr:
+            call("mfnerf_field_fw_lograd", ptr(t.feat), cap, ptr(m.dirs), cap, ptr(m.counter), ptr(self.packed),
+                 c.rgb_width, ptr(t.sigma), ptr(t.lograd), s)
+            mark("field_fw")
+            self._tonemap_fw(mb, q)
+            mark("tonemap_fw")
+        else:
+            call("mfnerf_field_fw", ptr(t.feat), cap, ptr(m.dirs), cap, ptr(m.counter), ptr(self.packed), c.rgb_width,
+                 0, ptr(t.sigma), ptr(t.rgb_s), s)
+            mark("field_fw")
         # the background: three scalars, or (random_bg) the 3 floats the batch's draw left in mb.bg,
         # read by the _bg forms of the two loss-carrying kernels (every part reads the one colour)
         bg = self.bg_value
@@ -589,24 +718,32 @@ class TrainStep:
                  ptr(t.sigma), ptr(t.rgb_s), ptr(t.ws), ptr(m.deltas), ptr(m.ts), ptr(m.rays_a), ptr(t.opacity),
                  ptr(t.depth), ptr(t.rgb), Np, cap, c.T_threshold, ptr(t.dsig), ptr(t.drgb_s), s)
             mark("composite_bw")
+        lograd = ""
+        if c.hdr:
+            self._tonemap_bw(mb, q)
+            mark("tonemap_bw")
+            lograd = "_lograd"  # the head's output gradient is dL/dlograd, no y(1-y)
         bw_args = (ptr(t.feat), cap, ptr(m.dirs), cap, ptr(m.counter), ptr(self.packed), c.rgb_width,
-                   ptr(t.dsig), ptr(t.drgb_s), 0.0 if c.dynamic_loss_scale else self.grad_scale, ptr(t.dfeat),
+                   ptr(t.dsig), ptr(t.dlograd if c.hdr else t.drgb_s),
+                   0.0 if c.dynamic_loss_scale else self.grad_scale, ptr(t.dfeat),
                    None if store_fold else ptr(t.mlp_grad), None if store_fold else ptr(t.mlp_grad[self.off_rgb:]),
                    ptr(t.field_ws), self._amp_ptr(), ptr(self._level_l1) if self._fixed() else None)
         if c.ray_grads:
             # the same backward plus dL/ddirs, then dL/dxyz through the encoding summed per ray
             # (the table is the fp16 copy the forward gathered from: Adam comes later in the step)
-            call("mfnerf_field_bw_inputs", *bw_args, ptr(t.ddirs), s)
+            call("mfnerf_field_bw_inputs" + lograd, *bw_args, ptr(t.ddirs), s)
             call("mfnerf_rays_input_grad", ptr(m.xyzs), ptr(m.ts), ptr(t.dfeat), ptr(t.ddirs), ptr(m.rays_a), Np, cap,
                  self.x_min, self.x_range, self.desc, ptr(self.p16[self.off_table:]), ptr(t.dL_drays_o),
                  ptr(t.dL_drays_d), s)
         else:
-            call("mfnerf_field_bw", *bw_args, s)
+            call("mfnerf_field_bw" + lograd, *bw_args, s)
         if store_fold:  # the fold writes the MLPs' gradient outright (nothing zeroed it)
             call("mfnerf_field_bw_reduce_store", c.rgb_width, ptr(t.field_ws), ptr(t.mlp_grad),
                  ptr(t.mlp_grad[self.off_rgb:]), self._amp_ptr(), s)
         if c.refine_poses:
             self._pose_update(mb)
+        if c.hdr and side_adam:
+            self._tm_update()
         mark("field_bw")
 
     def _fixed(self):
@@ -813,6 +950,7 @@ class TrainStep:
         step's generator after the noise."""
         mark = mark or _nomark
         self._check_bg(bg)
+        self._check_hdr(exchange)
         if self.cfg.refine_poses:
             self._check_refine(exchange)
             if batch is not None:
@@ -823,6 +961,8 @@ class TrainStep:
         if prepped:
             batch = self._sampled
             self._draw(batch, mb)
+        elif self.cfg.hdr:
+            self._stage_exposure(batch, mb)
         self._use(mb)
         self.last_batch = batch
         self._primed = False  # a pipelined replay() must march its own batch next
@@ -831,7 +971,7 @@ class TrainStep:
             self._dp_backward(batch, mb, mark)
         else:
             for q in range(self.n_parts):
-                self._chain(batch, mb, q, mark)
+                self._chain(batch, mb, q, mark, side_adam=optimize)
                 self._grid_bw(mb, q)
                 mark("grid_bw")
                 self._grid_finish(q)
@@ -968,6 +1108,7 @@ class TrainStep:
         batch's colour waits in set 1-j.
         Call after at least one eager step (lazy library init happens outside capture)."""
         self._check_refine()
+        self._check_hdr()
         self._flush_pack()
         self._capture_setup(host_noise)
         torch.cuda.synchronize()
@@ -1082,6 +1223,8 @@ class TrainStep:
             elif batch is not None:
                 for d, s_ in zip((dst.rays_o, dst.rays_d, dst.rgb), (batch.rays_o, batch.rays_d, batch.rgb)):
                     d.copy_(s_)
+            if self.cfg.hdr and batch is not None:
+                self._stage_exposure(batch, self.mbuf[j])
             if self._host_noise:
                 if noise is None:
                     raise ValueError("captured with host_noise: pass noise= / next_noise= to replay()")
@@ -1107,6 +1250,7 @@ class TrainStep:
         bg / next_bg: their background colours (random_bg, capture(host_noise=True), no dataset)."""
         j = self._parity
         self._check_refine(exchange)
+        self._check_hdr(exchange)
         self._check_bg(bg, next_bg)
         if self.dataset is not None:
             batch = None

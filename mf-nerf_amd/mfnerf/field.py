@@ -106,6 +106,19 @@ def field_fw(feat, dirs, n, packed, rgb_width=64, density_only=False, n_dev=None
     return sigma, rgb
 
 
+def field_fw_lograd(feat, dirs, n, packed, rgb_width=64, n_dev=None, sigma=None, lograd=None, plane_stride=0):
+    """mfnerf_field_fw_lograd: the head without its sigmoid (NGP(rgb_act='None')) -> sigma (n) f32,
+    lograd (n,3) f16."""
+    dev = feat.device
+    if sigma is None:
+        sigma = torch.empty(n, dtype=torch.float32, device=dev)
+    if lograd is None:
+        lograd = torch.empty(n, 3, dtype=torch.float16, device=dev)
+    call("mfnerf_field_fw_lograd", ptr(feat), int(plane_stride), ptr(dirs), int(n), ptr(n_dev), ptr(packed),
+         int(rgb_width), ptr(sigma), ptr(lograd), stream())
+    return sigma, lograd
+
+
 def field_bw_workspace(n, rgb_width=64, device="cuda"):
     nb = load().mfnerf_field_bw_workspace(int(n), int(rgb_width))
     return torch.empty(nb // 4, dtype=torch.float32, device=device)

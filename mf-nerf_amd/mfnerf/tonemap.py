@@ -63,6 +63,47 @@ def tonemap_bw(lograd16, exposure, e_stride, params, rgb16, dL_drgb):
     return dx, g
 
 
+# ---------------------------------------------------------------- the fused training step's forms
+def live_workspace(cap, device):
+    """The backward's workspace for a capacity of `cap` samples (C = 3; any content)."""
+    return torch.empty(max(16, load().mfnerf_tonemap_bw_workspace(cap, 3)), dtype=torch.uint8, device=device)
+
+
+def tonemap_fw_live(lograd16, exposure_s, n_dev, params, rgb):
+    """mfnerf_tonemap_fw_live: lograd16 (cap,3) f16, exposure_s (cap) f32 or None, n_dev (1) i32 on the
+    device, params (3*2048) f32 -> rgb (cap,3) f32 (half values), rows below min(cap, *n_dev)."""
+    call("mfnerf_tonemap_fw_live", ptr(lograd16), ptr(exposure_s), 0 if exposure_s is None else 1, lograd16.shape[0],
+         ptr(n_dev), ptr(params), ptr(rgb), stream())
+    return rgb
+
+
+def tonemap_bw_live(lograd16, exposure_s, n_dev, params, rgb, dL_drgb, dL_dlograd, grad_params, workspace):
+    """mfnerf_tonemap_bw_live into dL_dlograd (cap,3) f32 and grad_params (3*2048) f32 (overwritten)."""
+    call("mfnerf_tonemap_bw_live", ptr(lograd16), ptr(exposure_s), 0 if exposure_s is None else 1, lograd16.shape[0],
+         ptr(n_dev), ptr(params), ptr(rgb), ptr(dL_drgb), ptr(dL_dlograd), ptr(grad_params), ptr(workspace), stream())
+
+
+def expand_exposure(exposure_ray, rays_a, n_dev, exposure_s):
+    """mfnerf_expand_exposure (rendering.py:142-145): exposure_s[start:start+count] = exposure_ray[ray]
+    per row (ray, start, count) of rays_a, below min(cap, *n_dev)."""
+    call("mfnerf_expand_exposure", ptr(exposure_ray), ptr(rays_a), rays_a.shape[0], exposure_s.shape[0], ptr(n_dev),
+         ptr(exposure_s), stream())
+    return exposure_s
+
+
+def unit_loss(params, target, grad_params, loss_out, amp=None):
+    """mfnerf_tonemap_unit_loss (train.py:172-177), C = 3: loss_out (3) stored, its gradient added to
+    grad_params (3*2048); amp: the step's mfnerf_amp_state (8 x i32) or None."""
+    call("mfnerf_tonemap_unit_loss", ptr(params), 3, float(target), ptr(grad_params), ptr(loss_out), ptr(amp),
+         stream())
+
+
+def side_adam_step(params, grads, m, v, lr, betas, eps, step_dev, lr_dev=None, amp=None):
+    """mfnerf_side_adam_step: Adam on a small parameter group with its own device step counter."""
+    call("mfnerf_side_adam_step", ptr(params), ptr(grads), ptr(m), ptr(v), params.numel(), float(lr),
+         float(betas[0]), float(betas[1]), float(eps), ptr(step_dev), ptr(lr_dev), ptr(amp), stream())
+
+
 class TonemapFunction(torch.autograd.Function):
     """rgb (n, C) f16 = the C tonemappers of `params` (C * 2048 values, channel-major) on
     lograd (n, C) + log(exposure); exposure None, one value or one per sample.  The exposure gets no

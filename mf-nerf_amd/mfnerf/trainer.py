@@ -20,6 +20,11 @@ the step.
   by the launch that draws the step's batch (so a replayed step reads the colour of the batch it
   trains on, not of the batch drawn ahead); the draw is a counter hash of (dataset seed, draw count),
   not torch.rand's stream.  Synthetic scenes ignore the flag; test-time rendering keeps its black;
+* HDR / exposure -- --use_exposure (train.py:73,102-103,172-177): NGP(rgb_act='None') inside the fused step
+  (StepConfig.hdr): the training set carries one exposure per image and its unit_exposure_rgb, every
+  ray trains at its image's exposure, the loss has the unit-exposure term, and the three tonemappers
+  are a side parameter group sharing the field's Adam settings, schedule and GradScaler skip;
+  evaluate / validate take one exposure per view; checkpoints carry model.tonemapper_net_{i}.params;
 * metrics -- train loss / PSNR / rm_s (train.py:178-189), read back only every `log_every` steps;
   test PSNR with the test-time renderer (evaluate, train.py:197-206) and test PSNR + SSIM
   (validate, train.py:198-237: mfnerf.metrics, fp64 on the device, one read-back per test set);
@@ -81,9 +86,13 @@ class Trainer:
     def __init__(self, hp: HParams, train, device="cuda", rank=0, world=1, graphs=True):
         if hp.rgb_layers != 2:
             raise NotImplementedError("the fused field head implements rgb_layers=2")
-        if getattr(hp, "use_exposure", False):
-            raise NotImplementedError("use_exposure: the fused training step's field kernels apply the sigmoid; the "
-                                      "HDR/exposure model (NGP(rgb_act='None')) trains through rendering.render()")
+        hdr = bool(getattr(hp, "use_exposure", False))
+        if hdr and getattr(train, "exposure", None) is None:
+            raise NotImplementedError("use_exposure: the HDR/exposure model trains on a set that carries one exposure "
+                                      "per image (DeviceDataset(exposure=...)); this training set has none")
+        if hdr and world > 1:
+            raise NotImplementedError("use_exposure (the HDR/exposure model) runs on one GPU: the tonemappers' "
+                                      "gradient is not exchanged between ranks")
         if hp.optimize_ext and world > 1:
             raise NotImplementedError("optimize_ext (pose refinement) runs on one GPU: the per-image offsets are "
                                       "not exchanged between ranks")
@@ -91,7 +100,8 @@ class Trainer:
         cfg = engine.StepConfig(n_rays=hp.batch_size, scale=hp.scale, L=hp.L, F=hp.F, log2_T=hp.T, N_min=hp.N_min,
                                 N_max=hp.N_max, grid=hp.grid, N_tables=hp.N_tables, rgb_width=hp.rgb_channels,
                                 lr=hp.lr, lambda_distortion=hp.distortion_loss_w, refine_poses=hp.optimize_ext,
-                                pose_lr=hp.pose_lr, random_bg=hp.random_bg)
+                                pose_lr=hp.pose_lr, random_bg=hp.random_bg, hdr=hdr,
+                                **({"unit_exposure_rgb": train.unit_exposure_rgb} if hdr else {}))
         self.step = engine.TrainStep(cfg, device=device, seed=hp.seed)
         if world > 1:
             self.step.shard_optimizer(rank, world)
@@ -173,7 +183,7 @@ class Trainer:
         """An mfnerf.networks.NGP holding this trainer's current weights and occupancy."""
         from .networks import NGP
         st, hp = self.step, self.hp
-        m = NGP(scale=hp.scale, hparams=hp).to(st.dev)
+        m = NGP(scale=hp.scale, hparams=hp, rgb_act="None" if st.cfg.hdr else "Sigmoid").to(st.dev)
         self._store_into(m)
         return m
 
@@ -186,29 +196,43 @@ class Trainer:
         m.rgb_net.params.copy_(p[st.off_rgb:st.off_table])
         m.density_grid.copy_(st.density_grid)
         m.density_bitfield.copy_(st.bitfield)
+        if st.cfg.hdr:
+            for i in range(3):
+                getattr(m, f"tonemapper_net_{i}").params.copy_(st.tm_params[i])
 
     @torch.no_grad()
-    def evaluate(self, images, poses, directions, chunk=None, fused=False):
+    def evaluate(self, images, poses, directions, chunk=None, fused=False, exposures=None):
         """Mean test PSNR over views (train.py:197-206): the test-time renderer (rendering.py:46-118)
         on every pixel of each (images[i], poses[i]) view; also returns the per-view values.
-        fused=True renders with the single-launch kernel (rendering.render_fused) instead of the loop."""
+        fused=True renders with the single-launch kernel (rendering.render_fused) instead of the loop.
+        exposures: one per view (train.py:102-103), for a use_exposure model; None renders at unit
+        exposure."""
         from .data import get_rays
         from .rendering import render, render_fused
         model = self.to_ngp()
         dev = self.step.dev
         dirs = directions.to(dev)
         vals = []
-        for img, pose in zip(images, poses):
+        for i, (img, pose) in enumerate(zip(images, poses)):
             o, d = get_rays(dirs, pose.to(dev))
             kw = {} if fused else {"test_time": True}
             if self.hp.scale > 0.5:
                 kw["exp_step_factor"] = 1 / 256
+            kw.update(self._exposure_kw(exposures, i))
             res = render_fused(model, o, d, **kw) if fused else render(model, o, d, **kw)
             vals.append(psnr(res["rgb"].float(), img.to(dev)))
         return sum(vals) / len(vals), vals
 
+    def _exposure_kw(self, exposures, i):
+        """render()'s exposure= of view i (train.py:102-103: one value for the whole view)."""
+        if exposures is None:
+            return {}
+        if not self.step.cfg.hdr:
+            raise ValueError("exposures= is for a use_exposure model")
+        return {"exposure": torch.as_tensor(exposures[i], dtype=torch.float32, device=self.step.dev).reshape(1, 1)}
+
     @torch.no_grad()
-    def validate(self, images, poses, directions, img_wh=None, fused=False):
+    def validate(self, images, poses, directions, img_wh=None, fused=False, exposures=None):
         """validation_step / validation_epoch_end (train.py:198-237): test PSNR and SSIM of every
         (images[i], poses[i]) view, rendered exactly as evaluate() renders it, and their means over
         the views.  Each view's [mse, ssim] (metrics.image_metrics, fp64) goes into its row of one
@@ -231,6 +255,7 @@ class Trainer:
             kw = {} if fused else {"test_time": True}
             if self.hp.scale > 0.5:
                 kw["exp_step_factor"] = 1 / 256
+            kw.update(self._exposure_kw(exposures, i))
             res = render_fused(model, o, d, **kw) if fused else render(model, o, d, **kw)
             image_metrics(res["rgb"].float().contiguous(), img.to(dev, torch.float32).contiguous(), img_wh,
                           out=table[i], workspace=ws)
@@ -295,6 +320,15 @@ class Trainer:
         # ... and a fresh GradScaler (PL precision=16 builds it at init 2^16, train.py:287): the
         # loss scale, growth tracker and skip count do not carry over
         st.reset_loss_scale()
+        if st.cfg.hdr:  # the tonemappers (the reference's keys), fresh moments and step count like the field's
+            for i in range(3):
+                tm = sd[f"model.tonemapper_net_{i}.params"].float().to(st.dev)
+                if tm.numel() != st.tm_params[i].numel():
+                    raise ValueError("checkpoint does not match this model's configuration")
+                st.tm_params[i].copy_(tm)
+            st.tm_m.zero_()
+            st.tm_v.zero_()
+            st.tm_step_dev.zero_()
         if "model.density_grid" in sd:
             st.density_grid.copy_(sd["model.density_grid"].to(st.dev))
         if "model.density_bitfield" in sd:

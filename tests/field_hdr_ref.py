@@ -1,0 +1,124 @@
+"""The NGP field head WITHOUT its output sigmoid (NGP(rgb_act='None'), networks.py:134-155; csrc/field.hip's
+LOGRAD instantiations: mfnerf_field_fw_lograd, mfnerf_field_bw_lograd, mfnerf_field_bw_inputs_lograd)
+in float64, on top of tests/field_ref.py: the same fp16 points, float64 products and sums.
+
+    forward(feat16, dirs, px, pr, width)       -> sigma (N), lograd (N,3) = half((r2 @ R3^T)[:, :3]), acts
+    backward(acts, dL_dsigma, dL_dlograd, S)   -> field_ref.backward with dO = half(g * S)
+    dsh(acts, dL_dlograd, S)                   -> dL/dSH (N,16), for the direction gradient
+
+backward is field_ref.backward itself, handed activations whose `rgb` is 1/2 and four times the
+gradient: dO = half(4 g * S * 1/2 * 1/2) = half(g * S) exactly (powers of two), in float64 and in the
+fp32 emulation oracle.field_oracle.ngp_field_bw16 alike.  So order_sensitivity is field_ref's method.
+
+This module owns the inputs of tests/test_gpu_field_hdr.py (field_ref.seam_inputs at the seeds below,
+its dL_drgb draw taken as dL/dlograd; the base block, launch and regions are field_ref's), and
+tests/test_field_hdr_ref_cpu.py asserts their order sensitivity below field_ref.ORDER_LIMIT.
+"""
+import torch
+
+import field_ref as R
+from oracle import field_oracle as FO
+
+F64 = R.F64
+# Seeds from the same CPU search as field_ref's (running this file prints the table for seeds 1..39):
+# the seeds with the lowest worst case over the cases the GPU file runs (small N; base block, the
+# ragged_tile and pass_boundary regions; dL/dSH of the small N).  Over those seeds the worst case of a
+# width is 2e-5..7e-4 (single fp16 roundings) or above 1.9e-3 (a ReLU gate flipped: 5 of 39 seeds at
+# width 64, 17 of 39 at width 128).  Chosen: small N 1.9e-5 | 5.2e-5, base block and regions
+# 8.3e-5 | 1.18e-4 (width 64 | 128).
+SMALL_SEED = {64: 36, 128: 29}
+BASE_SEED = {64: 19, 128: 28}
+REGIONS = ("ragged_tile", "pass_boundary")
+
+
+def lograd_of(acts):
+    """The head's three outputs rounded to half (tcnn's fp16 output), in the activations' dtype."""
+    a = acts
+    return (a["r2"] @ a["R3"].t())[:, :3].half().to(a["r2"].dtype)
+
+
+def forward(feat16, dirs, px, pr, width=64):
+    sigma, _, acts = R.forward(feat16, dirs, px, pr, width)
+    return sigma, lograd_of(acts), acts
+
+
+def _unit(acts):
+    """acts with y (1 - y) = 1/4 exactly."""
+    return {**acts, "rgb": torch.full_like(acts["rgb"], 0.5)}
+
+
+def backward(acts, dL_dsigma, dL_dlograd, S=R.S):
+    return R.backward(_unit(acts), dL_dsigma, 4 * dL_dlograd, S)
+
+
+def backward_fp32(acts32, dL_dsigma, dL_dlograd, S=R.S):
+    """The fp32-sum emulation (oracle.field_oracle.ngp_field_bw16) of the same backward."""
+    return FO.ngp_field_bw16(_unit(acts32), dL_dsigma, 4 * dL_dlograd, S)
+
+
+def dsh(acts, dL_dlograd, S=R.S):
+    """dL/dSH (N,16): backward's chain up to dR1, then columns [:16] of dR1 @ R1, unscaled, in the
+    activations' dtype (float64 from forward(); fp32 sums from ngp_field_fw16's)."""
+    a = acts
+    dt = a["r2"].dtype
+    h = lambda t: t.half().to(dt)  # noqa: E731
+    dO = torch.zeros(a["r2"].shape[0], 16, dtype=dt)
+    dO[:, :3] = dL_dlograd.to(dt) * S
+    dr2 = h((h(dO) @ a["R3"]) * (a["r2"] > 0))
+    dr1 = h((dr2 @ a["R2"]) * (a["r1"] > 0))
+    return (dr1 @ a["R1"])[:, :16] / S
+
+
+def order_sensitivity_acts(a32, a64, dL_dsigma, dL_dlograd, S=R.S, idx=None):
+    """field_ref.order_sensitivity_acts for the no-activation backward."""
+    return R.order_sensitivity_acts(_unit(a32), _unit(a64), dL_dsigma, 4 * dL_dlograd, S, idx)
+
+
+def dsh_sensitivity(a32, a64, dL_dlograd, S=R.S):
+    lo, hi = dsh(a32, dL_dlograd, S), dsh(a64, dL_dlograd, S)
+    return float((lo.to(F64) - hi).abs().max() / hi.abs().max())
+
+
+def base_block(width):
+    """The base block (field_ref.BASE_N samples at BASE_SEED) and both forwards, once per width."""
+    if width not in _base_cache:
+        inp = R.seam_inputs(R.BASE_N, BASE_SEED[width], width)
+        feat, dirs, px, pr = inp[:4]
+        _, _, a32 = FO.ngp_field_fw16(feat, dirs, px, pr, width)
+        sig, lograd, a64 = forward(feat, dirs, px, pr, width)
+        _base_cache[width] = dict(inputs=inp, a32=a32, a64=a64, sigma=sig, lograd=lograd)
+    return _base_cache[width]
+
+
+_base_cache = {}
+
+
+def worst_sensitivities(G, width, small_seed, base_seed):
+    """Every precondition of the GPU file at these seeds: {case: sensitivities}."""
+    out = {}
+    for n in R.SMALL_NS:
+        feat, dirs, px, pr, dsig, dlog = R.seam_inputs(n, small_seed, width)
+        _, _, a32 = FO.ngp_field_fw16(feat, dirs, px, pr, width)
+        _, _, a64 = forward(feat, dirs, px, pr, width)
+        out[f"small_{n}"] = order_sensitivity_acts(a32, a64, dsig, dlog)
+        out[f"dsh_{n}"] = (dsh_sensitivity(a32, a64, dlog),)
+    feat, dirs, px, pr, dsig, dlog = R.seam_inputs(R.BASE_N, base_seed, width)
+    _, _, a32 = FO.ngp_field_fw16(feat, dirs, px, pr, width)
+    _, _, a64 = forward(feat, dirs, px, pr, width)
+    out["base_block"] = order_sensitivity_acts(a32, a64, dsig, dlog)
+    for name, _, lo, hi, _ in R.regions(G, width):
+        if name in REGIONS:
+            out[name] = order_sensitivity_acts(a32, a64, dsig, dlog, idx=torch.arange(lo, hi) % R.BASE_N)
+    return out
+
+
+if __name__ == "__main__":  # the seed search: python tests/field_hdr_ref.py
+    from mfnerf._lib import load
+    for width in (64, 128):
+        G = load().mfnerf_field_bw_slab_rows(width)
+        for seed in range(1, 40):
+            w = worst_sensitivities(G, width, seed, seed)
+            small = max(max(v) for k, v in w.items() if k.startswith(("small_", "dsh_")))
+            big = max(max(v) for k, v in w.items() if not k.startswith(("small_", "dsh_")))
+            print(f"width {width} seed {seed}: small N worst {small:.2e}, base block and regions worst {big:.2e}",
+                  flush=True)
