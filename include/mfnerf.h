@@ -622,6 +622,42 @@ int64_t mfnerf_image_metrics_workspace(int64_t H, int64_t W);
 int mfnerf_image_metrics(const float* pred, const float* target, int64_t H, int64_t W, double* out,
                          void* workspace, mfnerf_stream_t stream);
 
+/* ---------------------------------------------------------------- viewer frames */
+
+/* One whole view's rays from a camera pose (datasets/ray_utils.py:8-47 get_ray_directions plus
+ * :50-70 get_rays, which show_gui.py:74-75 re-runs per frame).  K4 = (fx, fy, cx, cy), four HOST
+ * floats read during the call; pose = a DEVICE pointer to the row-major (3,4) camera-to-world matrix,
+ * read by the kernel, so a replayed graph sees the pose its buffer holds then.  Pixel i = v*W + u gets
+ * the camera direction d = (((u - cx) + 0.5)/fx, ((v - cy) + 0.5)/fy, 1), IEEE fp32 divisions;
+ *   rays_d[i] = d . R^T (row a: fma(1, R[a][2], fma(dy, R[a][1], dx*R[a][0]))),  rays_o[i] = pose[:, 3]
+ * copied bit for bit.  out: rays_o, rays_d (W*H, 3) f32.  W*H outside 1..2^29, a null pointer or a
+ * zero focal length: MFN_ERR_INVALID, nothing is launched. */
+int mfnerf_camera_rays(const float* K4, const float* pose, int64_t W, int64_t H, float* rays_o, float* rays_d,
+                       mfnerf_stream_t stream);
+
+/* Workspace bytes of mfnerf_frame_finish (mode 1; a constant). */
+int64_t mfnerf_frame_finish_workspace(void);
+/* A rendered view's sums to a displayable frame (show_gui.py:90-99 render_cam's tail and the save
+ * branch of train.py:220-226).  opacity, depth (n) and rgb (n,3) f32 are what mfnerf_render_test_fused
+ * wrote: rgb BEFORE the background blend.  frame_u8 (n,3) u8, 4-byte aligned; frame_f32 (n,3) f32
+ * optional (NULL: not written), the GUI's float texture.
+ * mode 0, colour: c = rgb + bg*(1 - opacity), the fp32 expression of rendering.py:93-94 (bg: 1 for
+ *   exp_step_factor == 0, else 0; bg = 0 leaves an already blended rgb as it is); frame_f32 = c;
+ *   frame_u8 = (c*255).astype(uint8) of train.py:223 -- the fp32 product truncated toward zero --
+ *   except where that cast is undefined or wraps: a product outside [0, 256) is clamped to [0, 255]
+ *   and NaN gives 0.  Reads opacity and rgb only.
+ * mode 1, depth: depth2img (train.py:48-53): mn, mx over the n depths, x = (depth - mn)/(mx - mn)
+ *   (one IEEE fp32 division), k = uint8(x*255) as above, frame_u8 = TURBO[k] in R,G,B order (the
+ *   table of csrc/turbo_table.hpp; the reference's cv2 returns B,G,R); frame_f32 = frame_u8/255
+ *   (show_gui.py:99).  mx == mn (the reference divides 0 by 0): k = 0 everywhere.  Depths are taken
+ *   to be finite.  Reads depth only.  workspace: mfnerf_frame_finish_workspace() bytes, 4-byte
+ *   aligned, any contents: a first launch writes every word the second one reads (per-workgroup
+ *   min / max, no atomics), so the same bits on every run.
+ * n == 0 is a no-op; an unknown mode, n outside 0..2^29, a null pointer the mode reads or a
+ * misaligned frame_u8 / workspace: MFN_ERR_INVALID, nothing is launched. */
+int mfnerf_frame_finish(const float* opacity, const float* depth, const float* rgb, int64_t n, int mode, float bg,
+                        void* workspace, uint8_t* frame_u8, float* frame_f32, mfnerf_stream_t stream);
+
 /* ---------------------------------------------------------------- mesh extraction */
 
 /* A triangle mesh of the density field (test.ipynb, the "mesh" cell: model.density on an N^3 lattice,

@@ -7,6 +7,7 @@ Drop-in layers (same names and behaviour as the reference):
   mfnerf.networks.NGP       <- models/networks.py (tcnn modules replaced by fused HIP kernels)
   mfnerf.losses             <- losses.py
   mfnerf.tcnn               <- the tinycudann subset MF-NeRF configures
+  mfnerf.viewer             <- show_gui.py's OrbitCamera and frame path (render_cam), no window
 Fast path: mfnerf.engine.TrainStep (device-resident sample counts, no host syncs).
 All GPU work goes through libmfnerf_hip.so (include/mfnerf.h); there is no CPU fallback.
 """

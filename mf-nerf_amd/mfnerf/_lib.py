@@ -69,6 +69,9 @@ SIGNATURES = {
                                       ctypes.POINTER(GridDesc), _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "mfnerf_image_metrics_workspace": (_I64, [_I64, _I64]),
     "mfnerf_image_metrics": (_I, [_P, _P, _I64, _I64, _P, _P, _P]),
+    "mfnerf_camera_rays": (_I, [_P, _P, _I64, _I64, _P, _P, _P]),
+    "mfnerf_frame_finish_workspace": (_I64, []),
+    "mfnerf_frame_finish": (_I, [_P, _P, _P, _I64, _I, _F, _P, _P, _P, _P]),
     "mfnerf_mesh_lattice_points": (_I, [_P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P]),
     "mfnerf_mesh_count": (_I, [_P, _I64, _I64, _I64, _F, _P, _P, _P]),
     "mfnerf_mesh_emit": (_I, [_P, _I64, _I64, _I64, _F, _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -13,6 +13,9 @@ from .custom_functions import RayAABBIntersector, RayMarcher, VolumeRenderer
 
 MAX_SAMPLES = 1024
 NEAR_DISTANCE = 0.01
+# what render_fused and everything built on it (viewer.FrameRenderer) say to an HDR model
+HDR_GAP = ("render_fused: the single-launch renderer's field head applies the sigmoid; an "
+           "HDR/exposure model (rgb_act='None') renders with render(test_time=True)")
 
 
 def render(model, rays_o, rays_d, **kwargs):
@@ -110,8 +113,7 @@ def render_fused(model, rays_o, rays_d, **kwargs):
     from . import field
     from ._lib import call, check_input, ptr, stream
     if getattr(model, "rgb_act", "Sigmoid") != "Sigmoid":
-        raise NotImplementedError("render_fused: the single-launch renderer's field head applies the sigmoid; an "
-                                  "HDR/exposure model (rgb_act='None') renders with render(test_time=True)")
+        raise NotImplementedError(HDR_GAP)
     rays_o = rays_o.contiguous()
     rays_d = rays_d.contiguous()
     check_input("rays_o", rays_o, torch.float32)

@@ -232,12 +232,17 @@ class Trainer:
         return {"exposure": torch.as_tensor(exposures[i], dtype=torch.float32, device=self.step.dev).reshape(1, 1)}
 
     @torch.no_grad()
-    def validate(self, images, poses, directions, img_wh=None, fused=False, exposures=None):
+    def validate(self, images, poses, directions, img_wh=None, fused=False, exposures=None, save_dir=None):
         """validation_step / validation_epoch_end (train.py:198-237): test PSNR and SSIM of every
         (images[i], poses[i]) view, rendered exactly as evaluate() renders it, and their means over
         the views.  Each view's [mse, ssim] (metrics.image_metrics, fp64) goes into its row of one
         device tensor that is read back once after the last view: no host synchronisation between
         the renders.  img_wh = (W, H) defaults to the training set's.
+        save_dir: also write every view's prediction as {idx:03d}.png and its depth map as
+        {idx:03d}_d.png there (train.py:220-226, the reference's default; --no_save_test turns it
+        off), both quantised on the device by viewer.frame_finish -- the depth map in RGB Turbo
+         -- and written with PIL; each view's two frames are read back, so
+        this costs a host synchronisation per view.  None changes nothing, the launch sequence included.
         Returns {"psnr", "ssim", "psnr_per_view", "ssim_per_view"}."""
         from .data import get_rays
         from .metrics import image_metrics, psnr_from_mse, workspace_bytes
@@ -250,6 +255,16 @@ class Trainer:
         dirs = directions.to(dev)
         table = torch.empty(len(images), 2, dtype=torch.float64, device=dev)
         ws = torch.empty(workspace_bytes(img_wh[1], img_wh[0]), dtype=torch.uint8, device=dev)
+        if save_dir is not None:
+            import os
+            from PIL import Image
+            from .viewer import finish_workspace, frame_finish
+            os.makedirs(save_dir, exist_ok=True)
+            n_pix = img_wh[0] * img_wh[1]
+            # two allocations: frame_finish wants each frame 4-byte aligned, which a slice of one
+            # (2, n_pix, 3) tensor is not when 3 * n_pix is no multiple of 4
+            frames = [torch.empty(n_pix, 3, dtype=torch.uint8, device=dev) for _ in range(2)]  # colour, depth
+            frame_ws = finish_workspace(dev)
         for i, (img, pose) in enumerate(zip(images, poses)):
             o, d = get_rays(dirs, pose.to(dev))
             kw = {} if fused else {"test_time": True}
@@ -259,6 +274,14 @@ class Trainer:
             res = render_fused(model, o, d, **kw) if fused else render(model, o, d, **kw)
             image_metrics(res["rgb"].float().contiguous(), img.to(dev, torch.float32).contiguous(), img_wh,
                           out=table[i], workspace=ws)
+            if save_dir is not None:
+                # res["rgb"] is already blended with the background: bg = 0 leaves it as it is
+                rgb, depth = res["rgb"].float().contiguous(), res["depth"].float().contiguous()
+                frame_finish(res["opacity"].float().contiguous(), depth, rgb, "rgb", 0.0, frame_u8=frames[0])
+                frame_finish(None, depth, None, "depth", frame_u8=frames[1], workspace=frame_ws)
+                host = [f.cpu().numpy().reshape(img_wh[1], img_wh[0], 3) for f in frames]
+                Image.fromarray(host[0]).save(os.path.join(save_dir, f"{i:03d}.png"))
+                Image.fromarray(host[1]).save(os.path.join(save_dir, f"{i:03d}_d.png"))
         table[:, 0] = psnr_from_mse(table[:, 0])
         host = table.cpu()  # the one read
         psnrs, ssims = host[:, 0].tolist(), host[:, 1].tolist()
