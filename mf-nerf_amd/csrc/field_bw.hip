@@ -1,33 +1,29 @@
-// field.hip -- NGP field head on gfx950 MFMA: the two tiny-cuda-nn FullyFusedMLPs of
-// models/networks.py:36-79 (xyz: 32->64->16; rgb: [SH4(16) | h(16)] -> W -> W -> 3 with
-// W = rgb_channels in {64, 128} (opt.py:87; the MF benchmark scripts use 128), ReLU, bias-free,
-// fp16 operands / fp32 accumulation), TruncExp on h[0] and the SH4 direction encoding, forward
-// and backward.
+// field_bw.hip -- the backward of the NGP field head (the networks, the forward and the MFMA layout:
+// field_fw.hip; the recomputed forward: field_fwd.hpp; the weight fragments: field_pack.hpp).
 //
-// Layout (one wave = one tile of 32 samples, v_mfma_f32_32x32x16_f16):
-//   activations are kept TRANSPOSED -- channel on the MFMA row, sample on the lane (col = lane&31)
-//   -- so layer k's fp32 accumulator, ReLU'd and packed to f16, IS layer k+1's B operand with no
-//   LDS round trip (cdna_hip_programming.md section 3, "An accumulator tile as the next MFMA's
-//   operand").  The weights are the A operands, pre-permuted once per optimizer step by
-//   mfnerf_field_pack_weights into 1-KiB lane-linear fragments (ds_read_b128, conflict-free).
-//   Backward: see the comment above field_bw_coop_kernel.
-#include <type_traits>
-
+// Data gradients chain through accumulators exactly like the forward ("T" orientation: channel on
+// the MFMA row, sample on the lane).  Weight gradients dW = dY^T X reduce over SAMPLES, which must
+// therefore sit in the MFMA K dimension, i.e. inside each lane's registers -- the transpose of the
+// T operands, the "S" orientation (channel on the lane, samples in the registers): each T chunk is
+// written to a per-wave LDS tile image and read back with the transposing ds_read_b64_tr_b16
+// (t_put / s_get below; exact, no wave-level synchronisation).
+//   dW[out][in] (32x32 tile) += S(dY)[out-tile] x S(X)[in-tile], K = the tile's 32 samples (2 MFMAs)
+// The dW tiles accumulate across all sample tiles a workgroup processes (persistent grid) in
+// registers, split over its waves (field_bw_coop_kernel), then one slab row per workgroup, summed
+// in a fixed order by slab_reduce_kernel.
 #include "common.hpp"
 #include "mfma_pack.hpp"
 #include "field_pack.hpp"
 #include "field_fwd.hpp"
+#include "field_width.hpp"
 #include "../../include/mfnerf.h"
 
 using namespace mfn;
 using namespace mfn_field;
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 namespace {
 
-// Backward: 4 waves per workgroup, each the forward + data-gradient chain of its own 32-sample tile,
+// 4 waves per workgroup, each the forward + data-gradient chain of its own 32-sample tile,
 // the weight-gradient tiles split over the waves (field_bw_coop_kernel).
 // Rounds 1-4 held every tile in each wave (one wave per SIMD; at W = 128 a second pass recomputed the
 // forward for dWr2's 16 tiles: 0.46 vs 0.23 ms on the mf128 step, profiles/r05_v8_*).
@@ -35,14 +31,12 @@ namespace {
 // per sample tile; W = 128: 836 vs 171 us), dWr2 by LDS atomics beside the register tiles (3.4 ms
 // per 983k samples), Wr2^T read from global memory, two sample tiles per loop trip (~560 registers:
 // 80-147 spilled, 177 vs 122 us inside the step).
-// The weight gradients' operands need the samples in the MFMA K dimension: the TRANSPOSE of the
-// chain's T operands (channel on the row, sample on the lane).  Each T chunk goes to a per-wave LDS
-// image of the tile, [sample][channel] in 64-B rows of eight 8-B chunks (4 channels), the chunk index
-// XOR-swizzled with (row >> 1) & 7 (2-way bank conflicts on the writes, none on the reads), and comes
-// back with ds_read_b64_tr_b16, which hands each 16-lane group a 4-sample x 16-channel block column by
-// column (cdna_hip_programming.md T10).  The S operand's k order is the one the accumulator-as-operand
+// The transpose image of a tile: [sample][channel] in 64-B rows of eight 8-B chunks (4 channels), the
+// chunk index XOR-swizzled with (row >> 1) & 7 (2-way bank conflicts on the writes, none on the reads);
+// ds_read_b64_tr_b16 hands each 16-lane group a 4-sample x 16-channel block column by column
+// (cdna_hip_programming.md T10).  The S operand's k order is the one the accumulator-as-operand
 // packing has (element j of lane half h = sample 8(j>>2) + 4h + (j&3) of the k-step), so both operands
-// of every dW product agree.  Exact.  (Rounds 1-2 transposed on the matrix core instead: D = T x I,
+// of every dW product agree.  (Rounds 1-2 transposed on the matrix core instead: D = T x I,
 // 2 MFMAs + 8 packing instructions per tile, ~30 of the 98 MFMAs of a sample tile.)
 constexpr int TILE_HALFS = 32 * 32;
 constexpr size_t TILE_BYTES = TILE_HALFS * 2;
@@ -65,163 +59,6 @@ __device__ __forceinline__ void t_put(_Float16* slot, int lane, const half8& v, 
 __device__ __forceinline__ u32x2 tr_read(const _Float16* p) {
     typedef __attribute__((address_space(3))) short4v* lds_s4;
     return __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4)(p)));
-}
-
-struct SOp;
-__device__ __forceinline__ SOp s_get(const _Float16* slot, int lane);
-
-// tcnn SphericalHarmonics degree 4 as a module of its own (the tinycudann route's dir_encoder,
-// networks.py:60-67): in = (d/|d| + 1)/2 (n, 3) f32 -> (n, 16) f16, the IEEE operations and their
-// order of mfnerf/tcnn.py sh4_torch (no contraction), rounded to f16 once.  The fused field head
-// evaluates the same polynomial in-kernel (sh4 above).
-__global__ __launch_bounds__(256) void sh4_fw_kernel(const float* __restrict__ in, int64_t n,
-                                                     __half* __restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float x = in[3 * i] * 2.0f - 1.0f, y = in[3 * i + 1] * 2.0f - 1.0f, z = in[3 * i + 2] * 2.0f - 1.0f;
-    const float xy = x * y, xz = x * z, yz = y * z, x2 = x * x, y2 = y * y, z2 = z * z;
-    float o[16];
-    o[0] = 0.28209479177387814f;
-    o[1] = -0.48860251190291987f * y;
-    o[2] = 0.48860251190291987f * z;
-    o[3] = -0.48860251190291987f * x;
-    o[4] = 1.0925484305920792f * xy;
-    o[5] = -1.0925484305920792f * yz;
-    o[6] = 0.94617469575755997f * z2 - 0.31539156525251999f;
-    o[7] = -1.0925484305920792f * xz;
-    o[8] = 0.54627421529603959f * x2 - 0.54627421529603959f * y2;
-    o[9] = 0.59004358992664352f * y * (-3.0f * x2 + y2);
-    o[10] = 2.8906114426405538f * xy * z;
-    o[11] = 0.45704579946446572f * y * (1.0f - 5.0f * z2);
-    o[12] = 0.3731763325901154f * z * (5.0f * z2 - 3.0f);
-    o[13] = 0.45704579946446572f * x * (1.0f - 5.0f * z2);
-    o[14] = 1.4453057213202769f * z * (x2 - y2);
-    o[15] = 0.59004358992664352f * x * (-x2 + 3.0f * y2);
-    // each value rounded to f32 first, as torch does: an opaque use keeps the compiler from folding a
-    // product and its f16 conversion into one v_fma_mix (a single rounding of the exact product,
-    // which differs from torch's double rounding on ~1 value in 10^6)
-#pragma unroll
-    for (int k = 0; k < 16; ++k) asm volatile("" : "+v"(o[k]));
-    __half2* dst = reinterpret_cast<__half2*>(out + 16 * i);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) dst[k] = __floats2half2_rn(o[2 * k], o[2 * k + 1]);
-}
-
-template <typename TP, int W>
-__global__ void pack_kernel(const TP* __restrict__ px, const TP* __restrict__ pr, _Float16* __restrict__ out) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < Geo<W>::N * FRAG_HALFS) pack_elem<TP, W>(t, px, pr, out);
-}
-
-// feat layouts: plane_stride == 0 -> row-major (n, 32) f16 (tcnn's encoding output); > 0 ->
-// level-major planes (16, plane_stride) half2 (mfnerf_grid_encode_fw_planar).
-__device__ __forceinline__ void load_tile_in(const _Float16* __restrict__ feat, int64_t plane_stride,
-                                             const float* __restrict__ dirs, int64_t s, bool valid, int h,
-                                             bool want_dirs, TileIn& I) {
-    if (valid) {
-        if (plane_stride > 0) {
-            // x[0] element j = feature 8h+j = level 4h + j/2; x[1]: level 8 + 4h + j/2
-            const uint32_t* P = reinterpret_cast<const uint32_t*>(feat);
-            uint32_t u[8];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                u[k] = P[(int64_t)(4 * h + k) * plane_stride + s];
-                u[4 + k] = P[(int64_t)(8 + 4 * h + k) * plane_stride + s];
-            }
-            I.x[0] = *reinterpret_cast<const half8*>(&u[0]);
-            I.x[1] = *reinterpret_cast<const half8*>(&u[4]);
-        } else {
-            const half8* row = reinterpret_cast<const half8*>(feat + s * 32);
-            I.x[0] = row[h];
-            I.x[1] = row[2 + h];
-        }
-        if (want_dirs) { I.d[0] = dirs[3 * s]; I.d[1] = dirs[3 * s + 1]; I.d[2] = dirs[3 * s + 2]; }
-    } else {
-        I.x[0] = half8{}; I.x[1] = half8{};
-        I.d[0] = I.d[1] = I.d[2] = 0.0f;
-    }
-}
-
-// LOGRAD (mfnerf_field_fw_lograd): the rgb head without its sigmoid; `rgb` then points to an (n,3) f16
-// buffer, the log-radiance as tcnn returns it (the tonemap kernels' input)
-template <int W, bool DENSITY_ONLY, bool LOGRAD = false>
-__global__ __launch_bounds__(FIELD_BLOCK) void field_fw_kernel(const _Float16* __restrict__ feat,
-                                                                int64_t plane_stride,
-                                                                const float* __restrict__ dirs, int64_t n,
-                                                                const int32_t* __restrict__ n_dev,
-                                                                const _Float16* __restrict__ packed,
-                                                                float* __restrict__ sigma, float* __restrict__ rgb,
-                                                                const int32_t* __restrict__ cell,
-                                                                float* __restrict__ cell_out) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    _Float16* lds = reinterpret_cast<_Float16*>(smem);
-    load_frags(lds, packed, DENSITY_ONLY ? 8 : Geo<W>::N_FW);
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int r = lane & 31, h = lane >> 5;
-    const int64_t nn = n_dev ? min<int64_t>(n, (int64_t)*n_dev) : n;
-    const int64_t tiles = div_up<int64_t>(nn, 32);
-    // P tiles per trip (tile, tile + stride, ...), stage by stage (forward_tiles).  P = 2 measured no
-    // faster at W = 64 (28.7 vs 28 us: 204 registers, one wave per SIMD instead of two) and spills
-    // at W = 128
-    constexpr int P = 1;
-    const int64_t stride = (int64_t)gridDim.x * 4;
-    for (int64_t tile = (int64_t)blockIdx.x * 4 + wid; tile < tiles; tile += P * stride) {
-        TileIn I[P];
-        bool valid[P];
-#pragma unroll
-        for (int q = 0; q < P; ++q) {
-            const int64_t s = (tile + q * stride) * 32 + r;
-            valid[q] = s < nn;
-            load_tile_in(feat, plane_stride, dirs, s, valid[q], h, !DENSITY_ONLY, I[q]);
-        }
-        FwdTile<W> T[P];
-        forward_tiles<W, DENSITY_ONLY, P, true, LOGRAD>(lds, lane, I, valid, T);
-#pragma unroll
-        for (int q = 0; q < P; ++q) {
-            const int64_t s = (tile + q * stride) * 32 + r;
-            if (valid[q] && h == 0) {
-                const float sg = __expf(T[q].h0);  // TruncExp forward (custom_functions.py:166)
-                sigma[s] = sg;
-                if (DENSITY_ONLY && cell_out) {  // the occupancy refresh's density_grid_tmp[cell] = sigma
-                    const int32_t k = cell[s];
-                    if (k >= 0) cell_out[k] = sg;
-                }
-                if constexpr (LOGRAD) {
-                    _Float16* lograd = reinterpret_cast<_Float16*>(rgb);
-                    lograd[3 * s] = (_Float16)T[q].rgb[0];
-                    lograd[3 * s + 1] = (_Float16)T[q].rgb[1];
-                    lograd[3 * s + 2] = (_Float16)T[q].rgb[2];
-                } else if (!DENSITY_ONLY) {
-                    // tcnn returns fp16 rgb; the reference casts it to fp32 for compositing
-                    rgb[3 * s] = (float)(_Float16)T[q].rgb[0];
-                    rgb[3 * s + 1] = (float)(_Float16)T[q].rgb[1];
-                    rgb[3 * s + 2] = (float)(_Float16)T[q].rgb[2];
-                }
-            }
-        }
-    }
-}
-
-// ---------------------------------------------------------------- backward
-//
-// Data gradients chain through accumulators exactly like the forward ("T" orientation: channel on
-// the MFMA row, sample on the lane).  Weight gradients dW = dY^T X reduce over SAMPLES, which must
-// therefore sit in the MFMA K dimension, i.e. inside each lane's registers -- the transpose of the
-// T operands, the "S" orientation (channel on the lane, samples in the registers): each T chunk is
-// written to a per-wave LDS tile image and read back with the transposing ds_read_b64_tr_b16
-// (t_put / s_get above; exact, no wave-level synchronisation).
-//   dW[out][in] (32x32 tile) += S(dY)[out-tile] x S(X)[in-tile], K = the tile's 32 samples (2 MFMAs)
-// The dW tiles accumulate across all sample tiles a workgroup processes (persistent grid) in
-// registers, split over its waves (field_bw_coop_kernel), then one slab row per workgroup, summed
-// in a fixed order by slab_reduce_kernel.
-
-template <int W>
-__device__ __forceinline__ void load_frags_bw(_Float16* lds, const _Float16* __restrict__ packed) {
-    using G = Geo<W>;
-    const uint4* src = reinterpret_cast<const uint4*>(packed);
-    uint4* dst = reinterpret_cast<uint4*>(lds);
-    for (int i = threadIdx.x; i < G::N * 64; i += blockDim.x) dst[i] = src[i];
-    __syncthreads();
 }
 
 // S operands (K = samples 0..15 / 16..31 of the tile) of one 32-channel tile given as two T chunks
@@ -294,6 +131,7 @@ __device__ __forceinline__ void sh4_bw_dir(const f32x16& dsh, int h, float invS,
     const float nrm = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
     const float x = d[0] / nrm, y = d[1] / nrm, z = d[2] / nrm;
     const float xy = x * y, xz = x * z, yz = y * z, x2 = x * x, y2 = y * y, z2 = z * z;
+    // (sh4_poly's coefficients, field_fwd.hpp: this is its Jacobian)
     constexpr float c1 = 0.48860251190291987f, c2 = 1.0925484305920792f, c3 = 0.94617469575755997f,
                     c4 = 0.54627421529603959f, c5 = 0.59004358992664352f, c6 = 2.8906114426405538f,
                     c7 = 0.45704579946446572f, c8 = 0.3731763325901154f, c9 = 1.4453057213202769f;
@@ -376,7 +214,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CoopGeo<W>:
     constexpr size_t IMG_OFF = (size_t)G::N * FRAG_HALFS * 2;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     _Float16* lds_base = reinterpret_cast<_Float16*>(smem);
-    load_frags_bw<W>(lds_base, packed);
+    load_frags(lds_base, packed, G::N);
     const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (uniform)
     const int r = lane & 31, h = lane >> 5;
     const float S = scale_dev ? *scale_dev : grad_scale, invS = 1.0f / S;
@@ -400,21 +238,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CoopGeo<W>:
         const int64_t s = tile * 32 + r;
         const bool v = s < nn && h == 0;
         const int64_t sc = max<int64_t>(0, min<int64_t>(s, nn - 1));
-        if constexpr (PLANAR) {
-            const uint32_t* Pp = reinterpret_cast<const uint32_t*>(feat);
-            uint32_t u[8];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                u[k] = Pp[(int64_t)(4 * h + k) * plane_stride + sc];
-                u[4 + k] = Pp[(int64_t)(8 + 4 * h + k) * plane_stride + sc];
-            }
-            o.I.x[0] = *reinterpret_cast<const half8*>(&u[0]);
-            o.I.x[1] = *reinterpret_cast<const half8*>(&u[4]);
-        } else {
-            const half8* row = reinterpret_cast<const half8*>(feat + sc * 32);
-            o.I.x[0] = row[h];
-            o.I.x[1] = row[2 + h];
-        }
+        load_feat<PLANAR>(feat, plane_stride, sc, h, o.I.x);
         o.I.d[0] = dirs[3 * sc]; o.I.d[1] = dirs[3 * sc + 1]; o.I.d[2] = dirs[3 * sc + 2];
         o.gs = dL_dsigma[sc]; o.g0 = dL_drgb[3 * sc]; o.g1 = dL_drgb[3 * sc + 1]; o.g2 = dL_drgb[3 * sc + 2];
         o.live = v;
@@ -758,43 +582,12 @@ __global__ __launch_bounds__(256) void slab_reduce_kernel(const float* __restric
     }
 }
 
-bool width_ok(int w) { return w == 64 || w == 128; }
-
-int bad_width(int w) {
-    mfn_set_error("field: rgb_width=%d unsupported (this build: 64 or 128)", w);
-    return MFN_ERR_INVALID;
-}
-
-// f(std::integral_constant<int, W>{}) for a width that width_ok accepted: the one place that picks
-// between the two instantiations (as mlp_dispatch in mlp.hip)
-template <typename F>
-auto width_dispatch(int rgb_width, F&& f) -> decltype(f(std::integral_constant<int, 64>{})) {
-    if (rgb_width == 64) return f(std::integral_constant<int, 64>{});
-    return f(std::integral_constant<int, 128>{});
-}
-
-template <typename TP, int W>
-void launch_pack(const TP* px, const TP* pr, void* packed, mfnerf_stream_t stream) {
-    const int total = Geo<W>::N * FRAG_HALFS;
-    hipLaunchKernelGGL((pack_kernel<TP, W>), dim3((total + 255) / 256), dim3(256), 0, stream, px, pr,
-                       (_Float16*)packed);
-}
-
-template <int W, bool LOGRAD = false>
-void launch_fw(const void* feat, int64_t ps, const float* dirs, int64_t n, const int32_t* n_dev, const void* packed,
-               int density_only, float* sigma, float* rgb, mfnerf_stream_t stream, const int32_t* cell = nullptr,
-               float* cell_out = nullptr) {
-    const int64_t tiles = div_up<int64_t>(n, 32);
-    const int64_t want = div_up<int64_t>(tiles, 4);
-    const unsigned blocks = (unsigned)(want < 2048 ? want : 2048);
-    if (density_only)
-        hipLaunchKernelGGL((field_fw_kernel<W, true>), dim3(blocks), dim3(FIELD_BLOCK), 8 * FRAG_HALFS * 2, stream,
-                           (const _Float16*)feat, ps, dirs, n, n_dev, (const _Float16*)packed, sigma, rgb, cell,
-                           cell_out);
-    else
-        hipLaunchKernelGGL((field_fw_kernel<W, false, LOGRAD>), dim3(blocks), dim3(FIELD_BLOCK),
-                           (size_t)Geo<W>::N_FW * FRAG_HALFS * 2, stream, (const _Float16*)feat, ps, dirs, n, n_dev,
-                           (const _Float16*)packed, sigma, rgb, nullptr, nullptr);
+// the fold of the backward's slab (CoopGeo<W>::BLOCKS rows) into the gradients: added, or stored
+template <int W>
+void launch_slab_reduce(const void* workspace, float* grad_xyz, float* grad_rgb, int32_t* nonfinite, int store,
+                        mfnerf_stream_t stream) {
+    hipLaunchKernelGGL(slab_reduce_kernel<W>, dim3((Geo<W>::N_DW + 63) / 64), dim3(256), 0, stream,
+                       (const float*)workspace, CoopGeo<W>::BLOCKS, grad_xyz, grad_rgb, nonfinite, store);
 }
 
 // the cooperative backward of width W (row-major and planar kernels; workgroups = slab rows and LDS
@@ -808,7 +601,6 @@ int launch_bw(const void* feat, int64_t ps, const float* dirs, int64_t n, const 
               mfnerf_stream_t stream, float* dL_ddirs) {
     constexpr auto k0 = field_bw_coop_kernel<W, false, DDIRS, LOGRAD>, k1 = field_bw_coop_kernel<W, true, DDIRS, LOGRAD>;
     constexpr size_t lds = CoopGeo<W>::LDS;
-    constexpr int rows = CoopGeo<W>::BLOCKS;
     static const hipError_t attr = [] {
         const hipError_t a0 = hipFuncSetAttribute(reinterpret_cast<const void*>(k0),
                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -820,12 +612,10 @@ int launch_bw(const void* feat, int64_t ps, const float* dirs, int64_t n, const 
         mfn_set_error("field_bw: cannot raise the LDS limit to %d bytes", (int)lds);
         return MFN_ERR_INVALID;
     }
-    hipLaunchKernelGGL(ps > 0 ? k1 : k0, dim3(rows), dim3(256), lds, stream, (const _Float16*)feat, ps, dirs, n,
-                       n_dev, (const _Float16*)packed, dL_dsigma, dL_drgb, grad_scale, scale_dev, dL_dfeat,
+    hipLaunchKernelGGL(ps > 0 ? k1 : k0, dim3(CoopGeo<W>::BLOCKS), dim3(256), lds, stream, (const _Float16*)feat, ps,
+                       dirs, n, n_dev, (const _Float16*)packed, dL_dsigma, dL_drgb, grad_scale, scale_dev, dL_dfeat,
                        (float*)workspace, nonfinite, level_l1, dL_ddirs);
-    if (grad_xyz)
-        hipLaunchKernelGGL(slab_reduce_kernel<W>, dim3((Geo<W>::N_DW + 63) / 64), dim3(256), 0, stream,
-                           (const float*)workspace, rows, grad_xyz, grad_rgb, nonfinite, 0);
+    if (grad_xyz) launch_slab_reduce<W>(workspace, grad_xyz, grad_rgb, nonfinite, 0, stream);
     return MFN_OK;
 }
 
@@ -860,87 +650,6 @@ int field_bw_impl(const void* feat_f16, int64_t feat_plane_stride, const float* 
 }  // namespace
 
 extern "C" {
-
-int64_t mfnerf_field_packed_bytes(int rgb_width) {
-    if (!width_ok(rgb_width)) return -1;
-    return width_dispatch(rgb_width, [](auto w) { return (int64_t)Geo<decltype(w)::value>::N * FRAG_HALFS * 2; });
-}
-
-int mfnerf_field_pack_weights(const float* params_xyz, const float* params_rgb, int rgb_width, void* packed,
-                              mfnerf_stream_t stream) {
-    if (!width_ok(rgb_width)) return bad_width(rgb_width);
-    if (!params_xyz || !params_rgb || !packed) { mfn_set_error("field_pack_weights: null pointer"); return MFN_ERR_INVALID; }
-    width_dispatch(rgb_width, [&](auto w) { launch_pack<float, decltype(w)::value>(params_xyz, params_rgb, packed, stream); });
-    return mfn_check_launch("field_pack_weights");
-}
-
-int mfnerf_sh4_fw(const float* dirs01, int64_t n, void* out_f16, mfnerf_stream_t stream) {
-    if (n < 0 || (n > 0 && (!dirs01 || !out_f16))) { mfn_set_error("sh4_fw: bad arguments"); return MFN_ERR_INVALID; }
-    if (n == 0) return MFN_OK;
-    hipLaunchKernelGGL(sh4_fw_kernel, dim3((unsigned)div_up<int64_t>(n, 256)), dim3(256), 0, stream, dirs01, n,
-                       (__half*)out_f16);
-    return mfn_check_launch("sh4_fw");
-}
-
-int mfnerf_field_pack_weights_f16(const void* params_xyz_f16, const void* params_rgb_f16, int rgb_width, void* packed,
-                                  mfnerf_stream_t stream) {
-    if (!width_ok(rgb_width)) return bad_width(rgb_width);
-    if (!params_xyz_f16 || !params_rgb_f16 || !packed) { mfn_set_error("field_pack_weights_f16: null pointer"); return MFN_ERR_INVALID; }
-    const _Float16* px = (const _Float16*)params_xyz_f16;
-    const _Float16* pr = (const _Float16*)params_rgb_f16;
-    width_dispatch(rgb_width, [&](auto w) { launch_pack<_Float16, decltype(w)::value>(px, pr, packed, stream); });
-    return mfn_check_launch("field_pack_weights_f16");
-}
-
-int mfnerf_field_fw(const void* feat_f16, int64_t feat_plane_stride, const float* dirs, int64_t n,
-                    const int32_t* n_dev, const void* packed,
-                    int rgb_width, int density_only, float* sigma, float* rgb, mfnerf_stream_t stream) {
-    if (!width_ok(rgb_width)) return bad_width(rgb_width);
-    if (n < 0 || (feat_plane_stride != 0 && feat_plane_stride < n)) { mfn_set_error("field_fw: bad size"); return MFN_ERR_INVALID; }
-    if (n == 0) return MFN_OK;
-    if (!feat_f16 || !packed || !sigma || (!density_only && (!dirs || !rgb))) {
-        mfn_set_error("field_fw: null pointer"); return MFN_ERR_INVALID;
-    }
-    width_dispatch(rgb_width, [&](auto w) {
-        launch_fw<decltype(w)::value>(feat_f16, feat_plane_stride, dirs, n, n_dev, packed, density_only, sigma, rgb, stream);
-    });
-    return mfn_check_launch("field_fw");
-}
-
-int mfnerf_field_fw_lograd(const void* feat_f16, int64_t feat_plane_stride, const float* dirs, int64_t n,
-                           const int32_t* n_dev, const void* packed, int rgb_width, float* sigma, void* lograd_f16,
-                           mfnerf_stream_t stream) {
-    if (!width_ok(rgb_width)) return bad_width(rgb_width);
-    if (n < 0 || (feat_plane_stride != 0 && feat_plane_stride < n)) { mfn_set_error("field_fw_lograd: bad size"); return MFN_ERR_INVALID; }
-    if (n == 0) return MFN_OK;
-    if (!feat_f16 || !packed || !sigma || !dirs || !lograd_f16) {
-        mfn_set_error("field_fw_lograd: null pointer"); return MFN_ERR_INVALID;
-    }
-    width_dispatch(rgb_width, [&](auto w) {
-        launch_fw<decltype(w)::value, true>(feat_f16, feat_plane_stride, dirs, n, n_dev, packed, 0, sigma,
-                                            reinterpret_cast<float*>(lograd_f16), stream);
-    });
-    return mfn_check_launch("field_fw_lograd");
-}
-
-int mfnerf_field_fw_density_scatter(const void* feat_f16, int64_t feat_plane_stride, int64_t n, const int32_t* n_dev,
-                                    const void* packed, int rgb_width, float* sigma, const int32_t* cell_idx,
-                                    float* tmp, mfnerf_stream_t stream) {
-    if (!width_ok(rgb_width)) return bad_width(rgb_width);
-    if (n < 0 || (feat_plane_stride != 0 && feat_plane_stride < n)) {
-        mfn_set_error("field_fw_density_scatter: bad size");
-        return MFN_ERR_INVALID;
-    }
-    if (n == 0) return MFN_OK;
-    if (!feat_f16 || !packed || !sigma || !cell_idx || !tmp) {
-        mfn_set_error("field_fw_density_scatter: null pointer");
-        return MFN_ERR_INVALID;
-    }
-    width_dispatch(rgb_width, [&](auto w) {
-        launch_fw<decltype(w)::value>(feat_f16, feat_plane_stride, nullptr, n, n_dev, packed, 1, sigma, nullptr, stream, cell_idx, tmp);
-    });
-    return mfn_check_launch("field_fw_density_scatter");
-}
 
 int mfnerf_field_bw_slab_rows(int rgb_width) {
     if (!width_ok(rgb_width)) return -1;
@@ -999,9 +708,7 @@ static int field_bw_fold(int rgb_width, const void* workspace, float* grad_xyz, 
     if (!width_ok(rgb_width)) return bad_width(rgb_width);
     if (!workspace || !grad_xyz || !grad_rgb) { mfn_set_error("field_bw_reduce: null pointer"); return MFN_ERR_INVALID; }
     width_dispatch(rgb_width, [&](auto w) {
-        constexpr int W = decltype(w)::value;
-        hipLaunchKernelGGL(slab_reduce_kernel<W>, dim3((Geo<W>::N_DW + 63) / 64), dim3(256), 0, stream,
-                           (const float*)workspace, CoopGeo<W>::BLOCKS, grad_xyz, grad_rgb, nonfinite, store);
+        launch_slab_reduce<decltype(w)::value>(workspace, grad_xyz, grad_rgb, nonfinite, store, stream);
     });
     return mfn_check_launch("field_bw_reduce");
 }
@@ -1015,6 +722,5 @@ int mfnerf_field_bw_reduce_store(int rgb_width, const void* workspace, float* gr
                                  int32_t* nonfinite, mfnerf_stream_t stream) {
     return field_bw_fold(rgb_width, workspace, grad_xyz, grad_rgb, nonfinite, 1, stream);
 }
-
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // field_fwd.hpp -- the wave-level forward of the NGP field head (one wave = one tile of 32 samples,
-// v_mfma_f32_32x32x16_f16; layout and fragment order: field.hip, field_pack.hpp), shared by
-// field.hip and render.hip.
+// v_mfma_f32_32x32x16_f16; layout: field_fw.hip, fragment order: field_pack.hpp), shared by
+// field_fw.hip, field_bw.hip (its recomputation) and render.hip.
 #pragma once
 #include "common.hpp"
 #include "mfma_pack.hpp"
@@ -8,25 +8,16 @@
 
 namespace mfn_field {
 
+using mfn::lds_frag;
+using mfn::load_frags;
+using mfn::mfma;
 using mfn::pack8;
 
 constexpr int FIELD_BLOCK = 256;    // forward: 4 waves
 
-__device__ __forceinline__ f32x16 mfma(const half8& a, const half8& b, const f32x16& c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ half8 lds_frag(const _Float16* lds, int f, int lane) {
-    return *reinterpret_cast<const half8*>(lds + (f * 64 + lane) * 8);
-}
-
-// tcnn SphericalHarmonics degree 4 on in = (d/|d| + 1)/2, mapped back x = in*2-1 (networks.py:145-146)
-__device__ __forceinline__ void sh4(float dx, float dy, float dz, float* o) {
-    const float nrm = sqrtf(dx * dx + dy * dy + dz * dz);
-    float x = dx / nrm, y = dy / nrm, z = dz / nrm;
-    x = ((x + 1.0f) / 2.0f) * 2.0f - 1.0f;
-    y = ((y + 1.0f) / 2.0f) * 2.0f - 1.0f;
-    z = ((z + 1.0f) / 2.0f) * 2.0f - 1.0f;
+// The degree-4 spherical-harmonics polynomial of tcnn on the unit direction (x, y, z): the IEEE
+// operations and their order of mfnerf/tcnn.py sh4_torch.  (Its Jacobian: sh4_bw_dir, field_bw.hip.)
+__device__ __forceinline__ void sh4_poly(float x, float y, float z, float* o) {
     const float xy = x * y, xz = x * z, yz = y * z, x2 = x * x, y2 = y * y, z2 = z * z;
     o[0] = 0.28209479177387814f;
     o[1] = -0.48860251190291987f * y;
@@ -44,6 +35,16 @@ __device__ __forceinline__ void sh4(float dx, float dy, float dz, float* o) {
     o[13] = 0.45704579946446572f * x * (1.0f - 5.0f * z2);
     o[14] = 1.4453057213202769f * z * (x2 - y2);
     o[15] = 0.59004358992664352f * x * (-x2 + 3.0f * y2);
+}
+
+// tcnn SphericalHarmonics degree 4 on in = (d/|d| + 1)/2, mapped back x = in*2-1 (networks.py:145-146)
+__device__ __forceinline__ void sh4(float dx, float dy, float dz, float* o) {
+    const float nrm = sqrtf(dx * dx + dy * dy + dz * dz);
+    float x = dx / nrm, y = dy / nrm, z = dz / nrm;
+    x = ((x + 1.0f) / 2.0f) * 2.0f - 1.0f;
+    y = ((y + 1.0f) / 2.0f) * 2.0f - 1.0f;
+    z = ((z + 1.0f) / 2.0f) * 2.0f - 1.0f;
+    sh4_poly(x, y, z, o);
 }
 
 // Forward state of one tile that the backward needs again.
@@ -65,6 +66,29 @@ struct TileIn {
     half8 x[2];
     float d[3];
 };
+
+// TileIn::x of sample s on lane half h.  feat layouts: row-major (n, 32) f16 (tcnn's encoding
+// output), or PLANAR: level-major planes (16, plane_stride) half2 (mfnerf_grid_encode_fw_planar).
+template <bool PLANAR>
+__device__ __forceinline__ void load_feat(const _Float16* __restrict__ feat, int64_t plane_stride, int64_t s, int h,
+                                          half8* x) {
+    if constexpr (PLANAR) {
+        // x[0] element j = feature 8h+j = level 4h + j/2; x[1]: level 8 + 4h + j/2
+        const uint32_t* P = reinterpret_cast<const uint32_t*>(feat);
+        uint32_t u[8];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            u[k] = P[(int64_t)(4 * h + k) * plane_stride + s];
+            u[4 + k] = P[(int64_t)(8 + 4 * h + k) * plane_stride + s];
+        }
+        x[0] = *reinterpret_cast<const half8*>(&u[0]);
+        x[1] = *reinterpret_cast<const half8*>(&u[4]);
+    } else {
+        const half8* row = reinterpret_cast<const half8*>(feat + s * 32);
+        x[0] = row[h];
+        x[1] = row[2 + h];
+    }
+}
 
 // The forward of P independent tiles, stage by stage: each layer's MFMAs for every tile, then the
 // next layer.  The scheduler keeps this source order at one wave per SIMD, so a tile's packing
@@ -187,13 +211,6 @@ __device__ __forceinline__ void forward_tiles(const _Float16* lds, int lane, con
             if constexpr (LOGRAD) T[q].rgb[c] = o[q][c];
             else T[q].rgb[c] = 1.0f / (1.0f + __expf(-o[q][c]));
         }
-}
-
-__device__ __forceinline__ void load_frags(_Float16* lds, const _Float16* __restrict__ packed, int n_frags) {
-    const uint4* src = reinterpret_cast<const uint4*>(packed);
-    uint4* dst = reinterpret_cast<uint4*>(lds);
-    for (int i = threadIdx.x; i < n_frags * 64; i += blockDim.x) dst[i] = src[i];
-    __syncthreads();
 }
 
 }  // namespace mfn_field

@@ -1,10 +1,15 @@
-// field_pack.hpp -- the MFMA weight-fragment layout of field.hip (and the repack that builds it),
-// shared with grid_adam_fixed.hpp, whose optimizer tail repacks the MLP weights in its own launch.
+// field_pack.hpp -- the MFMA weight-fragment layout of the field head (field_fw.hip, field_bw.hip,
+// render.hip) and the repack that builds it, shared with grid_adam_fixed.hpp, whose optimizer tail
+// repacks the MLP weights in its own launch.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include "mfma_pack.hpp"
+
 namespace mfn_field {
+
+using mfn::k_of;
 
 constexpr int N_XYZ_PARAMS = 64 * 32 + 16 * 64;
 constexpr int FRAG_HALFS = 64 * 8;  // one A fragment: 64 lanes x 8 f16 (1 KiB)
@@ -59,9 +64,6 @@ __device__ __forceinline__ void mat_info(int mat, const TP* px, const TP* pr, co
         default: *p = pr + W * 32 + W * W; *rows = 16; *cols = W; break;
     }
 }
-
-// k index carried by element j of lane half h (natural B order, or accumulator-as-operand order)
-__device__ __forceinline__ int k_of(int j, int h, int perm) { return perm ? 8 * (j >> 2) + 4 * h + (j & 3) : 8 * h + j; }
 
 // one element t of the packed blob (t < Geo<W>::N * FRAG_HALFS) from the row-major weights
 template <typename TP, int W>

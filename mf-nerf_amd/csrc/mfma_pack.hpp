@@ -1,12 +1,35 @@
-// mfma_pack.hpp -- fp32 MFMA accumulator halves -> f16 B operands, with the ReLU and the ReLU
-// backward mask done on the packed halves (shared by field.hip and mlp.hip).
+// mfma_pack.hpp -- what every v_mfma_f32_32x32x16_f16 unit shares (field_fw.hip, field_bw.hip,
+// render.hip, mlp.hip): the operand types, the MFMA itself, the 1-KiB lane-linear weight fragments
+// in LDS (their k order, the copy into LDS, one lane's read), and fp32 accumulator halves -> f16 B
+// operands with the ReLU and the ReLU backward mask done on the packed halves.
 #pragma once
 #include <cstdint>
+#include <hip/hip_runtime.h>
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace mfn {
+
+__device__ __forceinline__ f32x16 mfma(const half8& a, const half8& b, const f32x16& c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+}
+
+// k index carried by element j of lane half h (natural B order, or accumulator-as-operand order)
+__device__ __forceinline__ int k_of(int j, int h, int perm) { return perm ? 8 * (j >> 2) + 4 * h + (j & 3) : 8 * h + j; }
+
+// the workgroup copies n_frags packed fragments (64 lanes x 8 f16 each) into LDS, then synchronises
+__device__ __forceinline__ void load_frags(_Float16* lds, const _Float16* __restrict__ packed, int n_frags) {
+    const uint4* src = reinterpret_cast<const uint4*>(packed);
+    uint4* dst = reinterpret_cast<uint4*>(lds);
+    for (int i = threadIdx.x; i < n_frags * 64; i += blockDim.x) dst[i] = src[i];
+    __syncthreads();
+}
+
+// this lane's 8 halves of fragment f (ds_read_b128, conflict-free)
+__device__ __forceinline__ half8 lds_frag(const _Float16* lds, int f, int lane) {
+    return *reinterpret_cast<const half8*>(lds + (f * 64 + lane) * 8);
+}
 
 typedef short short2v __attribute__((ext_vector_type(2)));
 typedef float float2v __attribute__((ext_vector_type(2)));

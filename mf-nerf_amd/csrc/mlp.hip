@@ -4,9 +4,10 @@
 // rgb_net 32 -> W -> W -> 3), i.e. what tinycudann.Network / NetworkWithInputEncoding compute when
 // the reference's own networks.py runs on this library (module swap).  The training
 // step does not use these kernels: it runs both MLPs fused with the SH encoding and TruncExp in
-// field.hip.  Same MFMA layout as field.hip (v_mfma_f32_32x32x16_f16; one wave = 32 samples;
+// field_fw.hip / field_bw.hip.  Same MFMA layout as theirs (v_mfma_f32_32x32x16_f16; one wave = 32 samples;
 // activations TRANSPOSED -- channel on the MFMA row, sample on the lane -- so a layer's
-// accumulator, activated and packed, is the next layer's B operand):
+// accumulator, activated and packed, is the next layer's B operand; the MFMA, the fragment copy and
+// read and the k order are mfma_pack.hpp's):
 //   forward : x (n, 32) f16 -> out (n, 16) f16 (tcnn pads the output width to 16);
 //   backward: recompute, chain the data gradients through the transposed weights (A fragments
 //             pre-permuted to the accumulator order), write dL/dx (n, 32) f32 and, per layer, the
@@ -19,9 +20,6 @@
 #include "../../include/mfnerf.h"
 
 using namespace mfn;
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
 
@@ -48,8 +46,6 @@ struct MG {
     static constexpr int ACT_ROWS = N_IN + NH * W;        // transposed layer inputs per sample
     static constexpr int DZ_ROWS = NH * W + N_OUT;        // transposed pre-activation grads per sample
 };
-
-__device__ __forceinline__ int k_of(int j, int h, int perm) { return perm ? 8 * (j >> 2) + 4 * h + (j & 3) : 8 * h + j; }
 
 // fragment f -> (matrix offset, rows, cols, transposed, row tile, k base, perm)
 template <int W, int NH>
@@ -82,12 +78,6 @@ __global__ void mlp_pack_kernel(const float* __restrict__ params, _Float16* __re
     out[t] = (_Float16)v;
 }
 
-__device__ __forceinline__ f32x16 mfma(const half8& a, const half8& b, const f32x16& c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ half8 frag(const _Float16* lds, int f, int lane) {
-    return *reinterpret_cast<const half8*>(lds + (f * 64 + lane) * 8);
-}
 // the forward of one 32-sample tile: the layer inputs as B operands (kept for the backward) and
 // the output layer's accumulator (rows 0..15)
 template <int W, int NH>
@@ -103,8 +93,8 @@ __device__ __forceinline__ void forward(const _Float16* lds, int lane, Fwd<W, NH
     const f32x16 z = {};
 #pragma unroll
     for (int mt = 0; mt < G::MT; ++mt) {
-        f32x16 a = mfma(frag(lds, G::F0 + 2 * mt, lane), T.x[0], z);
-        a = mfma(frag(lds, G::F0 + 2 * mt + 1, lane), T.x[1], a);
+        f32x16 a = mfma(lds_frag(lds, G::F0 + 2 * mt, lane), T.x[0], z);
+        a = mfma(lds_frag(lds, G::F0 + 2 * mt + 1, lane), T.x[1], a);
         T.a[0][2 * mt] = pack8<0, true>(a);
         T.a[0][2 * mt + 1] = pack8<8, true>(a);
     }
@@ -114,24 +104,17 @@ __device__ __forceinline__ void forward(const _Float16* lds, int lane, Fwd<W, NH
         for (int mt = 0; mt < G::MT; ++mt) {
             f32x16 a = z;
 #pragma unroll
-            for (int c = 0; c < G::KC; ++c) a = mfma(frag(lds, G::FH + ((l - 1) * G::MT + mt) * G::KC + c, lane), T.a[l - 1][c], a);
+            for (int c = 0; c < G::KC; ++c) a = mfma(lds_frag(lds, G::FH + ((l - 1) * G::MT + mt) * G::KC + c, lane), T.a[l - 1][c], a);
             T.a[l][2 * mt] = pack8<0, true>(a);
             T.a[l][2 * mt + 1] = pack8<8, true>(a);
         }
     f32x16 o = z;
 #pragma unroll
-    for (int c = 0; c < G::KC; ++c) o = mfma(frag(lds, G::FO + c, lane), T.a[NH - 1][c], o);
+    for (int c = 0; c < G::KC; ++c) o = mfma(lds_frag(lds, G::FO + c, lane), T.a[NH - 1][c], o);
     T.o = o;
 }
 
 __device__ __forceinline__ float out_act(float v, int oa) { return oa ? 1.0f / (1.0f + __expf(-v)) : v; }
-
-__device__ __forceinline__ void load_frags(_Float16* lds, const _Float16* __restrict__ packed, int n) {
-    const uint4* src = reinterpret_cast<const uint4*>(packed);
-    uint4* dst = reinterpret_cast<uint4*>(lds);
-    for (int i = threadIdx.x; i < n * 64; i += blockDim.x) dst[i] = src[i];
-    __syncthreads();
-}
 
 __device__ __forceinline__ void load_x(const _Float16* __restrict__ x, int64_t s, bool valid, int h, half8* xo) {
     const half8* row = reinterpret_cast<const half8*>(x + s * N_IN);
@@ -222,7 +205,7 @@ __global__ __launch_bounds__(MLP_BLOCK) void mlp_bw_kernel(const _Float16* __res
         half8 dzc[2 * (W / 32)];
 #pragma unroll
         for (int mt = 0; mt < G::MT; ++mt) {
-            f32x16 a = mfma(frag(lds, G::BO + mt, lane), d, z);
+            f32x16 a = mfma(lds_frag(lds, G::BO + mt, lane), d, z);
             dzc[2 * mt] = relu_mask8(pack8<0, false>(a), T.a[NH - 1][2 * mt]);
             dzc[2 * mt + 1] = relu_mask8(pack8<8, false>(a), T.a[NH - 1][2 * mt + 1]);
         }
@@ -235,7 +218,7 @@ __global__ __launch_bounds__(MLP_BLOCK) void mlp_bw_kernel(const _Float16* __res
             for (int mt = 0; mt < G::MT; ++mt) {
                 f32x16 a = z;
 #pragma unroll
-                for (int c = 0; c < G::KC; ++c) a = mfma(frag(lds, G::BH + ((l - 1) * G::MT + mt) * G::KC + c, lane), dzc[c], a);
+                for (int c = 0; c < G::KC; ++c) a = mfma(lds_frag(lds, G::BH + ((l - 1) * G::MT + mt) * G::KC + c, lane), dzc[c], a);
                 nx[2 * mt] = relu_mask8(pack8<0, false>(a), T.a[l - 1][2 * mt]);
                 nx[2 * mt + 1] = relu_mask8(pack8<8, false>(a), T.a[l - 1][2 * mt + 1]);
             }
@@ -247,7 +230,7 @@ __global__ __launch_bounds__(MLP_BLOCK) void mlp_bw_kernel(const _Float16* __res
         // dL/dx = W_0^T dZ_0 (rows = the 32 inputs)
         f32x16 a = z;
 #pragma unroll
-        for (int c = 0; c < G::KC; ++c) a = mfma(frag(lds, G::B0 + c, lane), dzc[c], a);
+        for (int c = 0; c < G::KC; ++c) a = mfma(lds_frag(lds, G::B0 + c, lane), dzc[c], a);
         if (valid) {
 #pragma unroll
             for (int g4 = 0; g4 < 4; ++g4)

@@ -1,5 +1,5 @@
-"""The NGP field head WITHOUT its output sigmoid (NGP(rgb_act='None'), networks.py:134-155; csrc/field.hip's
-LOGRAD instantiations: mfnerf_field_fw_lograd, mfnerf_field_bw_lograd, mfnerf_field_bw_inputs_lograd)
+"""The NGP field head WITHOUT its output sigmoid (NGP(rgb_act='None'), networks.py:134-155; the LOGRAD instantiations
+of csrc/field_fw.hip and field_bw.hip: mfnerf_field_fw_lograd, mfnerf_field_bw_lograd, mfnerf_field_bw_inputs_lograd)
 in float64, on top of tests/field_ref.py: the same fp16 points, float64 products and sums.
 
     forward(feat16, dirs, px, pr, width)       -> sigma (N), lograd (N,3) = half((r2 @ R3^T)[:, :3]), acts

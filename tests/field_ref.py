@@ -1,4 +1,4 @@
-"""The NGP field head (csrc/field.hip: xyz MLP 32->64->16, SH4, rgb MLP 32->W->W->3, TruncExp)
+"""The NGP field head (csrc/field_fw.hip, field_bw.hip: xyz MLP 32->64->16, SH4, rgb MLP 32->W->W->3, TruncExp)
 restated in plain torch with float64 accumulation, from the same fp16 points as the kernels.
 
 oracle/field_oracle.py's ngp_field_fw16 / ngp_field_bw16 round every operand to fp16 where tcnn and the

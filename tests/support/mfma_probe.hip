@@ -1,5 +1,5 @@
 // Test support (not part of the product library): one v_mfma_f32_32x32x16_f16 with A (32x16) and
-// B (16x32) f16 row-major -> D (32x32) f32, through the lane maps field.hip assumes (A: row = lane&31,
+// B (16x32) f16 row-major -> D (32x32) f32, through the lane maps field_fw.hip assumes (A: row = lane&31,
 // k = 8*(lane>>5) + j; B: col = lane&31, same k; D: row = (i&3) + 8*(i>>2) + 4*(lane>>5)).
 // Built by tests/support/Makefile into libmfnerf_probe.so; loaded by tests/test_gpu_field.py.
 #include <hip/hip_runtime.h>

@@ -1,4 +1,4 @@
-"""The field kernels without the output sigmoid (csrc/field.hip's LOGRAD instantiations:
+"""The field kernels without the output sigmoid (csrc/field_fw.hip's and field_bw.hip's LOGRAD instantiations:
 mfnerf_field_fw_lograd, mfnerf_field_bw_lograd, mfnerf_field_bw_inputs_lograd) against the float64
 reference tests/field_hdr_ref.py, at both widths, with row-major and with planar features.
 

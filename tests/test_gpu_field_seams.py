@@ -1,4 +1,4 @@
-"""The fused field MLP kernels (csrc/field.hip: field_fw_kernel, field_bw_coop_kernel +
+"""The fused field MLP kernels (csrc/field_fw.hip: field_fw_kernel; csrc/field_bw.hip: field_bw_coop_kernel +
 slab_reduce_kernel) at the seams of their persistent loops, against the float64-accumulated reference
 of tests/field_ref.py.
 
@@ -307,7 +307,7 @@ def test_bw_as_the_training_step_calls_it(gpu, width):
 @pytest.mark.parametrize("width", WIDTHS)
 def test_fw_two_trips(gpu, width):
     c = _ctx(width)
-    # launch_fw (csrc/field.hip) caps the grid at 2048 workgroups of 4 tiles of 32 samples: the
+    # launch_fw (csrc/field_fw.hip) caps the grid at 2048 workgroups of 4 tiles of 32 samples: the
     # grid-stride loop of field_fw_kernel takes a second trip only past 2048 * 128 samples
     n = 2048 * 128 + 173
     rows = R.tile_rows(n).to(gpu)

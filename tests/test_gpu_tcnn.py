@@ -7,7 +7,7 @@ time (what runs with sys.modules["tinycudann"] = mfnerf.tcnn).
   restatement), for every (width, hidden layers, output activation) MF-NeRF configures;
 * the three modules composed exactly as networks.py:134-155 (xyz_encoder -> TruncExp(h[:, 0]),
   SH4((d/|d| + 1)/2), rgb_net(cat[SH, h])) against the fused field head (mfnerf.networks.NGP,
-  field.hip) on the same parameters: sigma, rgb and the parameter gradients."""
+  field_fw.hip, field_bw.hip) on the same parameters: sigma, rgb and the parameter gradients."""
 import math
 
 import pytest
