@@ -209,7 +209,10 @@ int mfnerf_grid_encode_fw(const float* x, int64_t n, const int32_t* n_dev, float
 
 /* mfnerf_grid_encode_fw with a level-major output: out_planes (n_levels, plane_stride) half2, the
  * features of level l of point i at [l*plane_stride + i] (plane_stride >= n).  Work is split by
- * level over the 8 XCDs so each XCD's L2 holds only its levels' tables. */
+ * level over the 8 XCDs so each XCD's L2 holds only its levels' tables.  Every level needs
+ * size >= 2 entries (the kernel gathers 8 B at a time): a level of one entry is MFN_ERR_INVALID
+ * here, before any launch, while mfnerf_grid_encode_fw accepts it.  Entries of the planes at or
+ * past min(n, *n_dev) are left untouched. */
 int mfnerf_grid_encode_fw_planar(const float* x, int64_t n, const int32_t* n_dev, float x_min, float x_range,
                                  const mfnerf_grid_desc* desc, const void* table_f16, void* out_planes,
                                  int64_t plane_stride, mfnerf_stream_t stream);

@@ -184,6 +184,14 @@ int mfnerf_grid_encode_fw_planar(const float* x, int64_t n, const int32_t* n_dev
     int st = check_desc(desc, "grid_encode_fw_planar");
     if (st) return st;
     if (n < 0 || plane_stride < n) { mfn_set_error("grid_encode_fw_planar: bad size"); return MFN_ERR_INVALID; }
+    // planar_gather loads 8 B at min(idx, size - 2): a one-entry level would wrap the clamp and read
+    // past its table (grid_fw_kernel gathers entry by entry and takes such a level)
+    for (int l = 0; l < desc->n_levels; ++l)
+        if (desc->size[l] < 2u) {
+            mfn_set_error("grid_encode_fw_planar: level %d has %u entries, the planar forward needs >= 2", l,
+                          desc->size[l]);
+            return MFN_ERR_INVALID;
+        }
     if (n == 0) return MFN_OK;
     if (!x || !table_f16 || !out_planes) { mfn_set_error("grid_encode_fw_planar: null pointer"); return MFN_ERR_INVALID; }
     const int64_t want = div_up<int64_t>(n, ENC_BLOCK);

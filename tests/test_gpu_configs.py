@@ -20,6 +20,8 @@ import numpy as np
 import pytest
 import torch
 
+import grid_fw_ref as FW
+import input_grad_ref as IG
 from mfnerf import engine, synthetic
 from mfnerf.field import XYZ_NET_PARAMS
 from oracle import field_oracle as FO
@@ -117,6 +119,9 @@ def test_config_full_size_step_vs_oracle(gpu, oracle, name):
     feat_s = cpu(feat[idx.to(gpu)])
     enc_ref = FO.grid_encode(xn, table16, olay)
     assert torch.allclose(feat_s, enc_ref, atol=1e-3, rtol=0)
+    # the same subset to one fp16 rounding (tests/grid_fw_ref.py; the kernels' own fp32 normalisation)
+    x01 = IG.normalise(xyzs[idx], st.x_min, st.x_range)
+    FW.check(feat[idx.to(gpu)].cpu(), *FW.forward_ref(x01, table16.half(), olay), f"config {name} encoding", olay, x01)
 
     # --- field head forward on the subset, from the kernels' own features
     sig_ref, rgb_ref, acts = FO.ngp_field_fw16(feat_s.half(), dirs[idx], px, pr, cfg.rgb_width)

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import grid_fw_ref as FW
 from conftest import ROOT
 from field_ref import fp32_autograd as _fp32_autograd
 from mfnerf import field as FLD
@@ -102,6 +103,8 @@ def test_grid_encode_fw_bw(gpu, name, args):
     out = FLD.grid_encode_fw(x.to(gpu), N, table.half().to(gpu), lay, desc)
     # fp32 accumulation of fp16 corners, one fp16 rounding of the output: <= 1 fp16 ulp (|y| < 1)
     assert torch.allclose(out.float().cpu(), ref, atol=1e-3, rtol=0)
+    # ... and to that one rounding: the fp64 sum under the derived bound of tests/grid_fw_ref.py
+    FW.check(out.cpu(), *FW.forward_ref(x, table.half(), olay), f"grid_encode_fw {name}", olay, x)
     # backward: index_add (oracle autograd) vs fp32 atomics
     dy = torch.randn(N, lay.L * lay.F, generator=g)
     tp = table.clone().requires_grad_(True)
@@ -402,6 +405,8 @@ def test_grid_encode_world_coords_normalisation(gpu):
     ref = FO.grid_encode((xw - xmin) / (xmax - xmin), table, olay)  # networks.py:105
     out = FLD.grid_encode_fw(xw.to(gpu), 4096, table.half().to(gpu), lay, lay.desc(), -0.5, 1.0)
     assert torch.allclose(out.float().cpu(), ref, atol=1e-3, rtol=0)
+    x01 = (xw - xmin) / (xmax - xmin)
+    FW.check(out.cpu(), *FW.forward_ref(x01, table.half(), olay), "grid_encode_fw world coordinates", olay, x01)
 
 
 def _field_inputs(N, seed=4, wscale=3.0, width=64):
@@ -532,6 +537,7 @@ def test_planar_encode_and_field_match_row_major(gpu, name, args):
          torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
     assert torch.equal(planes[:, :N].permute(1, 0, 2).reshape(N, -1), row)
+    assert bool((planes[:, N:].view(torch.int16) == FW.NAN16).all()), "plane entries past the live count written"
     if lay.L != 16:
         return
     _, dirs, px, pr = _field_inputs(N, seed=12)

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import grid_fw_ref as FW
 import grid_plan_ref as GP
 import grid_seam_ref as GS
 import input_grad_ref as IG
@@ -96,6 +97,8 @@ def test_spotlights(gpu, name):
     out = FLD.grid_encode_fw(xg, N, t16, lay, desc)
     # fp32 accumulation of fp16 corners, one fp16 rounding of the output: <= 1 fp16 ulp (|y| < 1)
     assert torch.allclose(out.float().cpu(), ref, atol=1e-3, rtol=0)
+    ref64, A = FW.forward_ref(sp.x, table, olay)  # ... and to that one rounding (tests/grid_fw_ref.py)
+    FW.check(out.cpu(), ref64, A, f"spotlights {name}, row-major forward", olay, sp.x)
     cap = (N + 127) // 128 * 128
     xp = torch.zeros(cap, 3, device=gpu)
     xp[:N] = xg
@@ -105,6 +108,7 @@ def test_spotlights(gpu, name):
     torch.cuda.synchronize()
     pl = planes[:, :N].permute(1, 0, 2).reshape(N, -1)
     assert torch.allclose(pl.float().cpu(), ref, atol=1e-3, rtol=0)
+    FW.check(pl.cpu(), ref64, A, f"spotlights {name}, planar forward", olay, sp.x)
     dyf = torch.randn(N, 2 * lay.L, generator=g)
     dref, A = IG.dx_ref(sp.x, table, dyf, olay)
     got = FLD.grid_encode_bw_input(xg, N, t16, dyf.to(gpu), desc).cpu()
