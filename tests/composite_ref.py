@@ -84,6 +84,27 @@ def _ray64(sig, rgb, dl, t, thr):
     return total, L, w, w.sum(), (w * t[:L]).sum(), (w[:, None] * rgb[:L]).sum(0)
 
 
+def composite_test64(sigmas, rgbs, deltas, ts, n_eff, thr=T_THRESHOLD):
+    """Test-time compositing (volumerendering.cu:206-249 from opacity 0) in fp64 on the row-per-ray
+    layout of raymarching_test: sigmas, deltas, ts (n, S), rgbs (n, S, 3), n_eff (n) samples per row.
+    A sample is accumulated, then the ray stops when T <= thr (the terminating sample counts).
+    -> (opacity (n), depth (n), rgb (n, 3) fp64, count (n) int64 = samples accumulated)."""
+    S = sigmas.shape[1]
+    n_eff = n_eff.long()
+    if S == 0:
+        z = torch.zeros(sigmas.shape[0], dtype=torch.float64)
+        return z, z.clone(), torch.zeros(sigmas.shape[0], 3, dtype=torch.float64), n_eff.clone()
+    live = torch.arange(S)[None] < n_eff[:, None]
+    a = torch.where(live, 1 - torch.exp(-sigmas.double() * deltas.double()), torch.zeros((), dtype=torch.float64))
+    T_after = torch.cumprod(1 - a, 1)
+    stop = live & (T_after <= thr)
+    first = torch.where(stop.any(1), stop.int().argmax(1), torch.full_like(n_eff, S))
+    count = torch.minimum(first + 1, n_eff)
+    T_before = torch.cat([torch.ones_like(T_after[:, :1]), T_after[:, :-1]], 1)
+    w = torch.where(torch.arange(S)[None] < count[:, None], a * T_before, torch.zeros((), dtype=torch.float64))
+    return w.sum(1), (w * ts.double()).sum(1), (w[:, :, None] * rgbs.double()).sum(1), count
+
+
 def composite_fw64(sigmas, rgbs, deltas, ts, rays_a, thr=T_THRESHOLD):
     """-> dict(total int64, opacity, depth, rgb fp64 by ray id, ws fp64 per sample: 0 after
     termination and in the gaps)."""
